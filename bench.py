@@ -18,6 +18,14 @@ one Adam step on the encoder parameters.  The batches (4 distinct ones, rotated)
 in HBM before the timed region.  `value_cached_topology` is the same step replayed on ONE fixed
 batch with the adjacency built once outside the loop (round 1's headline).  Prints ONE JSON
 line (rank 0).
+
+A plain run sets up, warms up (`--settle` + `--warmup` untimed steps), times `--steps` steps
+and prints the headline line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, `config`).  `--full` adds everything else to that line: the extra windows,
+`value_cached_topology`, the rooflines with their rocprofv3 child passes, strict fp32, the
+drop-in wiring, merged branches, other backbones, radius100k, the full-model steps and the CPU
+baseline.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy;
+with the same arguments the inputs are the same in every run.
 """
 from __future__ import annotations
 
@@ -98,6 +106,15 @@ def parse():
                     help="N > 1: capture the gradient all-reduce + Adam inside the step's hipGraph (default: eager after it)")
     ap.add_argument("--distinct-batches", type=int, default=4,
                     help="batches rotated through the timed steps (each step sees a new edge_index)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline: the PMC / kernel-trace child passes, the extra "
+                         "windows, the cached-topology loop, rooflines, strict fp32, drop-in wiring, merged branches, "
+                         "other backbones, radius100k, full-model steps and the CPU baseline (each still has its --no-* "
+                         "switch); without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): "
+                         "the encoder outputs (a fixed, seeded row sample of each above 16 MB), the parameters after "
+                         "the Adam step and Adam's moments (or, with --no-optim, the parameter gradients)")
     return ap.parse_args()
 
 
@@ -851,6 +868,27 @@ def measure_kernel_only(batch: int, timeout_s: float = 300.0):
         shutil.rmtree(out, ignore_errors=True)
 
 
+def _row_sample(t: torch.Tensor, max_bytes: int = 16 << 20) -> torch.Tensor:
+    """`t` itself when its float32 rows fit in `max_bytes`, else a fixed sample of its rows (seed 0, in row order)."""
+    rows = max(1, max_bytes // (4 * max(t[0].numel(), 1)))
+    if t.shape[0] <= rows:
+        return t
+    idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:rows].sort().values
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(path: str, arrays: dict, limit_bytes: int = 64 << 20) -> None:
+    """`--dump-outputs`: every array as `path/<name>.npy` in float32, at most `limit_bytes` in all."""
+    import numpy as np
+    host = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > limit_bytes:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {limit_bytes})")
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def _capture(g):
     """Every hipGraph capture of this file: `dp.capture` - thread-local capture checks once a process group exists (RCCL's
     watchdog thread queries events while this thread captures; in the default mode that aborts the process)."""
@@ -909,13 +947,15 @@ def main():
     phase("start")
     traffic, traffic_note = None, "not measured at N > 1"
     kernel_only, kernel_only_note = None, "not measured"
-    if world == 1:
+    if world == 1 and args.full:
         traffic, traffic_note = (None, "--no-pmc") if args.no_pmc else measure_traffic()
         if not (args.no_kernel_trace or args.headline_only or args.workload != "everyday"):
             kernel_only, kernel_only_note = measure_kernel_only(args.batch)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device (no CPU fallback in deformcontact_amd)")
     if args.workload == "radius100k":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the everyday workload's step (not --workload radius100k)")
         torch.cuda.set_device(local_rank % max(torch.cuda.device_count(), 1))
         r = radius100k(torch.device("cuda", torch.cuda.current_device()), args.kernel_reps // 3 or 3)
         if rank == 0:
@@ -1010,11 +1050,16 @@ def main():
     k_hops = enc.conv_layers_resting[0].K
 
     model_box = [enc]                                  # the module a step runs (the drop-in leg swaps the wiring, same parameters)
+    # --dump-outputs: the encoder outputs of the latest step stay referenced (a captured step's outputs are then the
+    # graph's static tensors, rewritten by every replay); without it nothing is held, as before
+    last_out = [] if args.dump_outputs else None
 
     def fwd_bwd(slot=0):
         if opt is None:
             bucket.zero()
         a, b = model_box[0](*slots[slot])
+        if last_out is not None:
+            last_out[:] = (a, b)
         torch.autograd.backward([a, b], [g_rest, g_rig])
 
     ar_events = []                                     # HIP events around the gradient all-reduce (N > 1)
@@ -1165,11 +1210,26 @@ def main():
     elapsed = timed(serial_step, args.steps, warmup)
     ms_per_step = elapsed / args.steps * 1e3
     value = edges_per_rank * world * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the encoder outputs and the state the Adam step left (parameters,
+        # moments) - or, with --no-optim, the gradients in the bucket
+        torch.cuda.synchronize()
+        arrays = {"out_rest": _row_sample(last_out[0]), "out_rigid": _row_sample(last_out[1])}
+        names = {id(p): n for n, p in enc.named_parameters()}
+        for p, off in zip(bucket.params, bucket.offsets):
+            n, sl = names[id(p)], slice(off, off + p.numel())
+            if opt is None:
+                arrays["grad." + n] = bucket.flat[sl].view_as(p)
+            else:
+                arrays["param." + n] = opt.flat_param[sl].view_as(p)
+                arrays["adam_exp_avg." + n] = opt.exp_avg[sl].view_as(p)
+                arrays["adam_exp_avg_sq." + n] = opt.exp_avg_sq[sl].view_as(p)
+        dump_outputs(args.dump_outputs, arrays)
     # the same loop again, `--windows` more windows of K steps each (the driver's 20-step window is
     # 13 ms of a 40 s run; min / median over windows say how far one window can sit from the typical one).  `value` above
     # stays the FIRST window - the K steps the contract times.
     window_ms = [round(ms_per_step, 4)]
-    for _ in range(max(args.windows, 0)):
+    for _ in range(max(args.windows, 0) if args.full else 0):
         window_ms.append(round(timed(serial_step, args.steps, 0) / args.steps * 1e3, 4))
     if args.headline_only:
         if rank == 0:
@@ -1182,8 +1242,8 @@ def main():
             dist.destroy_process_group()
         return
     # ---- secondary: the per-batch topology work left out of the loop (round-1 headline definition) ----
-    elapsed_c = timed(make_mode("cached"), args.steps, warmup)
-    graph_used = len(captured) >= 2             # both modes really replay a captured graph
+    elapsed_c = timed(make_mode("cached"), args.steps, warmup) if args.full else None
+    graph_used = len(captured) >= (2 if args.full else 1)       # every mode timed really replays a captured graph
 
     out = {
         "metric": "M edges/sec fwd+bwd, everyday-deform batch=32 per GPU (encoder hot path)",
@@ -1197,12 +1257,6 @@ def main():
                  ("f32 (dense blocks bf16x3-split operands, 6 bf16 MFMA products, fp32 accumulate)" if ops.DENSE_SPLIT_BF16
                   else "f32"),
         "data": "synthetic",
-        "ms_per_step_windows": {"windows": len(window_ms), "steps_each": args.steps, "min": min(window_ms),
-                                "median": sorted(window_ms)[len(window_ms) // 2], "max": max(window_ms),
-                                "note": "window 0 is `ms_per_step` (the K steps the contract times); the others repeat the "
-                                        "same K-step loop in the same process"},
-        "value_cached_topology": round(edges_per_rank * world * args.steps / elapsed_c / 1e6, 3),
-        "ms_per_step_cached_topology": round(elapsed_c / args.steps * 1e3, 4),
         "dense_arithmetic": (("fp32 storage and accumulate; wide dense blocks as power-of-two-scaled 2-way "
                               "fp16 splits (3 fp16 MFMAs per product tile, fp32-accurate), narrow ones as "
                               "exact 3-way bf16 splits (6 bf16 MFMAs)") if ops.DENSE_F16X2 else
@@ -1221,8 +1275,6 @@ def main():
                     + ", the first-layer hop slabs are computed, then fwd + bwd(synthetic "
                     "upstream grad)" + (" + RCCL grad all-reduce" if dist_on else "")
                     + ("" if args.no_optim else " + Adam") + "; all of it inside the timed region, one hipGraph",
-            "value_cached_topology": "one fixed batch replayed, adjacency and first-layer hops built once "
-                                     "outside the loop (round-1 headline definition)",
             "hipgraph": graph_used, "two_stream_branches": not args.serial_branches,
             "merged_branches": bool(enc._mergeable(rest.x, rig.x)),
             "segmented_adjacency_build": all(getattr(g_, "_segments", None) is not None
@@ -1231,6 +1283,15 @@ def main():
         },
     }
 
+    if args.full:
+        out["ms_per_step_windows"] = {"windows": len(window_ms), "steps_each": args.steps, "min": min(window_ms),
+                                      "median": sorted(window_ms)[len(window_ms) // 2], "max": max(window_ms),
+                                      "note": "window 0 is `ms_per_step` (the K steps the contract times); the others "
+                                              "repeat the same K-step loop in the same process"}
+        out["value_cached_topology"] = round(edges_per_rank * world * args.steps / elapsed_c / 1e6, 3)
+        out["ms_per_step_cached_topology"] = round(elapsed_c / args.steps * 1e3, 4)
+        out["config"]["value_cached_topology"] = ("one fixed batch replayed, adjacency and first-layer hops built once "
+                                                  "outside the loop (round-1 headline definition)")
     if dist_on:
         torch.cuda.synchronize()
         us = sorted(a.elapsed_time(b) * 1e3 for a, b in ar_events[-max(args.steps, 1):])
@@ -1262,7 +1323,7 @@ def main():
                        "collective": "one all_reduce(AVG) per step over the flat fp32 gradient bucket "
                                      "(dp.GradBucket.all_reduce_mean), issued after the captured fwd+bwd; HIP events "
                                      "on rank 0's stream around the call, median / max over the timed steps"}
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: the F=256 hop as a step launches it
         # (k_spmm_wave<4,8,true>: the hop + the row maxima the dense block scales by; forward over
         # the sorted adjacency, backward - on the masked gradient - over the transposed one) ----
@@ -1533,6 +1594,7 @@ def main():
                 out["full_forward_b32"] = {"error": f"{type(e).__name__}: {e}"}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.batch, args.cpu_seconds, all_cores=args.cpu_all_cores)
+    if rank == 0:
         print(json.dumps(out), flush=True)
 
     phase("result line printed" if rank == 0 else "waiting for rank 0's kernel-level measurements")

@@ -220,11 +220,30 @@ def feature_rigid_fixture():
     print("wrote feature_rigid.npz")
 
 
+def reference_state_dict_fixture():
+    """The state_dict layout (keys in order, shapes) of the reference's own ``GraphNet`` as
+    ``models/model_loader.py`` builds it from ``configs/everyday.json``, with the PyG restatement
+    as ``torch_geometric`` - what a reference checkpoint holds.  ``tests/test_reference_alias.py``
+    checks this package's model against it without the reference checkout."""
+    from configs.config import Config
+    from models.model_loader import load_model
+    sd = load_model(Config(os.path.join(REF, "configs", "everyday.json"))).state_dict()
+    shapes = np.full((len(sd), 4), -1, np.int64)
+    for i, v in enumerate(sd.values()):
+        shapes[i, :v.dim()] = v.shape
+    np.savez_compressed(os.path.join(OUT, "reference_state_dict.npz"), keys=np.array(list(sd)),
+                        ndim=np.array([v.dim() for v in sd.values()], np.int64), shapes=shapes)
+    print("wrote reference_state_dict.npz")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     install_oracle_as_pyg()
     sys.path.insert(0, REF)
     torch.set_num_threads(1)       # deterministic CPU summation order for the fixtures
+    reference_state_dict_fixture()
+    if "--only-state-dict" in sys.argv:
+        return
     feature_rigid_fixture()
     if "--only-feature-rigid" in sys.argv:
         return

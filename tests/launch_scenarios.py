@@ -22,8 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RESULTS = {}
 SKIPPED = None          # reason the scenarios were not run (no GPU, HIP already initialised, DC_SKIP_LAUNCH=1)
 
-BENCH_ARGS = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--settle", "0", "--kernel-reps", "4", "--no-pmc", "--no-cpu-baseline",
-              "--no-full-step", "--no-strict-fp32", "--no-radius100k", "--no-merged", "--no-backbones"]
+BENCH_ARGS = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--settle", "0", "--kernel-reps", "4", "--full", "--no-pmc",
+              "--no-cpu-baseline", "--no-full-step", "--no-strict-fp32", "--no-radius100k", "--no-merged", "--no-backbones"]
 # (NCCL_SOCKET_IFNAME: RCCL bootstraps over sockets even on one node; the loopback interface keeps it off whatever else the
 # box has - bench.py sets the same default when the rendezvous address is a loopback one)
 DIAG_ENV = {"DC_RANK_WATCHDOG_S": "40", "DC_GLOO_TIMEOUT_S": "60", "NCCL_SOCKET_IFNAME": "lo"}

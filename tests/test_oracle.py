@@ -43,8 +43,34 @@ def test_config0_oracle_reproduces_reference_run(backbone, fname):
     assert abs(float(l1) - float(z["loss_l1"])) <= TOL * abs(float(z["loss_l1"]))
     assert abs(float(gcl) - float(z["loss_gcl"])) <= TOL * abs(float(z["loss_gcl"]))
     (l1 + gcl).backward()
+    truth64 = _float64_grads(backbone, z) if backbone == "GATConv" else None
     for name, p in m.named_parameters():
+        truth = truth64[name] if name.endswith("att_dst") else None
+        scale = np.abs(z["grad." + name.replace("att_dst", "att_src")]).max()
+        if truth is not None and np.abs(truth).max() < 1e-9 * scale:
+            # softmax is invariant to a per-destination shift: where d loss / d att_dst is zero in float64, both fp32
+            # gradients are rounding noise (~1e-13) whose bits depend on the CPU's vector kernels; as in
+            # test_gpu_parity, compared against float64 on the scale of the sibling att_src gradient
+            e_h = np.abs(p.grad.numpy() - truth).max()
+            e_o = np.abs(z["grad." + name] - truth).max()
+            assert e_h <= max(2 * e_o, 2e-5 * scale), (name, e_h, e_o, scale)
+            continue
         assert rel_err(p.grad, z["grad." + name]) < 2e-5, name
+
+
+def _float64_grads(backbone, z):
+    """The parameter gradients of the fixture's step, oracle convs in float64."""
+    from deformcontact_amd.graphnet import gradient_consistency_loss
+    m = _net(backbone, int(z["hidden"])).double().train()
+    rest, rig = golden_graphs(z)
+    for b in (rest, rig):
+        b.x, b.pos = b.x.double(), b.pos.double()
+    pred = m(rest, rig)
+    pred.pos = pred.pos - rest.pos
+    tgt = rest.clone()
+    tgt.pos = torch.from_numpy(z["def_pos"]).double() - rest.pos
+    (torch.nn.functional.l1_loss(pred.pos, tgt.pos) + gradient_consistency_loss(pred, tgt)).backward()
+    return {k: v.grad.numpy() for k, v in m.named_parameters()}
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])

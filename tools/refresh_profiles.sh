@@ -14,13 +14,13 @@ export TMPDIR=/tmp
 cd /tmp
 (cd "$R" && timeout -s KILL 1200 python -m pytest tests -m gpu -q > "$O/pytest.txt" 2>&1; tail -2 "$O/pytest.txt")
 (cd "$R" && timeout -s KILL 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.txt" 2>&1; tail -2 "$O/smoke.txt")
-(cd "$R" && S=$(date +%s) && timeout -s KILL 900 python bench.py > "$O/bench.json" 2> "$O/bench.err"; echo "bench wall $(( $(date +%s) - S )) s" | tee "$O/bench_wall.txt"; tail -c 300 "$O/bench.json")
+(cd "$R" && S=$(date +%s) && timeout -s KILL 900 python bench.py --full > "$O/bench.json" 2> "$O/bench.err"; echo "bench wall $(( $(date +%s) - S )) s" | tee "$O/bench_wall.txt"; tail -c 300 "$O/bench.json")
 (cd "$R" && timeout -s KILL 300 python tools/kbench.py > "$O/kbench.txt" 2>&1)
 Q="--no-cpu-baseline --no-full-step --no-strict-fp32 --no-radius100k --no-pmc --no-merged --no-backbones"
-timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/stats_serial" -- python3 "$R/bench.py" $Q --serial-branches > "$R/$O/stats_serial.log" 2>&1
-timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/stats_default" -- python3 "$R/bench.py" $Q > "$R/$O/stats_default.log" 2>&1
+timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/stats_serial" -- python3 "$R/bench.py" --full $Q --serial-branches > "$R/$O/stats_serial.log" 2>&1
+timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/stats_default" -- python3 "$R/bench.py" --full $Q > "$R/$O/stats_default.log" 2>&1
 # the GCNConv / GATConv encoders on the same batch (dc_gat_*, dc_sddmm_f32, self-loop adjacency build)
-timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/stats_backbones" -- python3 "$R/bench.py" --no-cpu-baseline --no-full-step --no-strict-fp32 --no-radius100k --no-pmc --no-merged --steps 5 --warmup 2 > "$R/$O/stats_backbones.log" 2>&1
+timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/stats_backbones" -- python3 "$R/bench.py" --full --no-cpu-baseline --no-full-step --no-strict-fp32 --no-radius100k --no-pmc --no-merged --steps 5 --warmup 2 > "$R/$O/stats_backbones.log" 2>&1
 # the whole reference step at B = 32 (attention kernels), eager
 timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/stats_full_b32" -- python3 "$R/tools/full_step.py" --batch 32 --steps 3 > "$R/$O/stats_full_b32.log" 2>&1
 timeout -s KILL 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --output-format csv -d "$R/$O/pmc_a" -- python3 "$R/tools/pmc_dense.py" > "$R/$O/pmc_a.log" 2>&1
@@ -55,7 +55,7 @@ done
 (cd "$R" && GRAFT_REPO_ROOT="$R" timeout -s KILL 300 bash tools/exp/csr_ab.sh DC_CSR_BUCKETS=0 DC_CSR_BUCKETS=1 > "$O/csr_build_windowed_vs_bucketed.txt" 2>&1)
 (cd "$R" && for b in 32 128; do for m in 0 1; do echo "== B=$b DC_CSR_BUCKETS=$m"; DC_CSR_BUCKETS=$m timeout -s KILL 200 python tools/exp/build_time.py $b 2>&1 | grep "us per build"; done; done > "$O/csr_build_mesh_batches.txt")
 for M in 0 1; do
-    (cd /tmp && DC_DW_BF16_DMA=$M timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/radius100k_dwdma$M" -- python3 "$R/bench.py" --workload radius100k --no-cpu-baseline > "$R/$O/radius100k_dwdma$M.log" 2>&1)
+    (cd /tmp && DC_DW_BF16_DMA=$M timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/radius100k_dwdma$M" -- python3 "$R/bench.py" --full --workload radius100k --no-cpu-baseline > "$R/$O/radius100k_dwdma$M.log" 2>&1)
 done
 # keep the summaries, drop the bulky per-dispatch traces (gpurun_out/ travels back, 64 MiB cap)
 find "$R/$O" -name "*kernel_trace.csv" -delete

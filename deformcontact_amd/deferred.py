@@ -6,14 +6,23 @@ epilogue and writes the result straight into the next layer's hop slab.  So that
 reaches that path, a plain PyG-style call returns a ``DeferredActivation``: a ``torch.Tensor`` subclass without
 storage that stands for the conv's output.  The first thing done to it decides how the layer runs:
 
-* ``F.relu(y)`` / ``torch.relu(y)`` / ``y.relu()`` (any of their in-place forms) - the layer runs ONCE with the
-  ReLU fused and that result is returned: no pre-activation tensor, no elementwise launch, no mask pass in backward;
-* anything else (``y.sum()``, ``y + 1``, ``y.detach()``, ``torch.cat([y, ...])``, ``y.data_ptr()`` ...) - the layer
-  runs without activation and the operation is applied to that tensor, exactly as if the conv had returned it.
+* ``F.relu(y)`` / ``torch.relu(y)`` / ``y.relu()`` - the layer runs ONCE with the ReLU fused and that result is
+  returned: no pre-activation tensor, no elementwise launch, no mask pass in backward.  A later plain use of ``y`` still
+  sees the pre-activation, so it runs the layer a second time, without activation;
+* the in-place forms (``y.relu_()``, ``torch.relu_(y)``, ``F.relu_(y)``, ``F.relu(y, inplace=True)``,
+  ``nn.ReLU(inplace=True)(y)``) - the layer runs once with the ReLU fused and ``y`` from then on stands for that
+  activated tensor, as the eager conv output would after an in-place ReLU; the plain tensor is returned.  Under
+  ``torch.no_grad()`` on a result that wants a gradient the layer runs without activation and the ReLU is applied to it
+  unrecorded, as in eager mode;
+* anything else (``y.sum()``, ``y + 1``, ``y.add_(1)``, ``y.detach()``, ``torch.cat([y, ...])``, ``y.data_ptr()`` ...) -
+  the layer runs without activation and the operation is applied to that tensor, exactly as if the conv had returned it.
+  Once that tensor exists, every later use of ``y`` - a ReLU, in-place or not, included - is the real operation on it:
+  the layer never runs again fused over an in-place edit.
 
 Shape, dtype, device and ``requires_grad`` are answered without running anything.  The value is computed in the grad
 mode and on the stream that are current when it is first needed - for the reference's ``F.relu(conv(...))`` that is
-the call site itself.  The two autograd entry points that take tensors without dispatching on them
+the call site itself - except that a call that wanted no gradient is never recorded, and one that did is recorded even
+when its first use is not.  The two autograd entry points that take tensors without dispatching on them
 (``torch.autograd.backward([y], ...)``, ``torch.autograd.grad(y, ...)``) need ``y.value()`` (they raise on the wrapper);
 ``y.backward(...)`` works as is.  ``deformcontact_amd.nn.conv.DEFER_ACTIVATION = False`` (or ``DC_DEFER_ACT=0``) turns the
 mechanism off: the conv then returns its output tensor directly and a following ``F.relu`` is a launch of its own.
@@ -24,6 +33,7 @@ import torch
 import torch.nn.functional as F
 
 _RELU_FUNCS = {F.relu, torch.relu, torch.Tensor.relu, torch.relu_, torch.Tensor.relu_, F.relu_}
+_RELU_INPLACE = {torch.relu_, torch.Tensor.relu_, F.relu_}
 
 #: answered from the wrapper's own metadata (no launch)
 _META = {"shape", "size", "dim", "ndim", "ndimension", "dtype", "device", "numel", "nelement", "is_cuda", "layout",
@@ -82,6 +92,9 @@ class DeferredActivation(torch.Tensor):
                         "tensor computed from y), or set deformcontact_amd.nn.conv.DEFER_ACTIVATION = False")
                 with torch.enable_grad():
                     v = self._dc_run(relu)
+            elif not self._dc_requires_grad and torch.is_grad_enabled():
+                with torch.no_grad():                            # (the eager call would not have been recorded)
+                    v = self._dc_run(relu)
             else:
                 v = self._dc_run(relu)
             self._dc_values[relu] = v
@@ -90,8 +103,16 @@ class DeferredActivation(torch.Tensor):
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
         kwargs = kwargs or {}
-        if func in _RELU_FUNCS and args and isinstance(args[0], cls):
-            return args[0].value(True)
+        if func in _RELU_FUNCS and args and isinstance(args[0], cls) and False not in args[0]._dc_values:
+            y = args[0]
+            inplace = func in _RELU_INPLACE or bool(kwargs.get("inplace", args[1] if len(args) > 1 else False))
+            if not inplace:
+                return y.value(True)
+            if True not in y._dc_values and not (y._dc_requires_grad and not torch.is_grad_enabled()):
+                v = y._dc_values[False] = y.value(True)           # y now aliases the activated tensor
+                return v
+            # the real in-place op on the pre-activation: F.relu(y) has already handed out the fused result (which must
+            # not change with y), or the ReLU is not recorded while the call was (eager backward has no mask there)
         name = _func_name(func)
         if name == "requires_grad" and len(args) == 1 and isinstance(args[0], cls):
             return args[0]._dc_requires_grad

@@ -443,17 +443,25 @@ def _alloc_slab(n: int, wpad: int, dev, tag=None) -> torch.Tensor:
     return base[:, :wpad] if pad else base
 
 
+_SLAB_CLAIMED = "_dc_hop_slab_claimed"
+
+
 def _as_slab_block0(x: torch.Tensor, n: int, fi: int, wpad: int):
     """If ``x`` is column block 0 of a ``[n, wpad]`` hop slab THIS LIBRARY allocated for it (the
-    previous layer's forward wrote its output there and tagged the buffer), return that slab (a
-    ``[n, wpad]`` view of the possibly row-padded buffer); else None.  Shape and stride alone are not
-    enough: a caller's own ``feat[:, :fi]`` view of a wider tensor looks the same, and the hops would
-    overwrite its other columns."""
+    previous layer's forward wrote its output there and tagged the buffer) and no layer has adopted
+    that slab yet, claim it and return it (a ``[n, wpad]`` view of the possibly row-padded buffer);
+    else None.  Shape and stride alone are not enough: a caller's own ``feat[:, :fi]`` view of a wider
+    tensor looks the same, and the hops would overwrite its other columns.  One adoption per slab: a
+    second consumer of the same output (two heads, two edge sets, one conv applied twice) would write
+    its hops over the ones the first saved for backward - the raw kernels bump no version counter, so
+    autograd would not notice - and packs a slab of its own instead."""
     base = x._base
     if (base is not None and getattr(base, _SLAB_TAG, None) == (n, fi, wpad)
+            and not getattr(base, _SLAB_CLAIMED, False)
             and base.dim() == 2 and base.size(0) == n and base.size(1) >= wpad
             and base.is_contiguous() and x.stride() == (base.size(1), 1) and x.shape == (n, fi)
             and x.data_ptr() == base.data_ptr() and base.dtype == torch.float32):
+        setattr(base, _SLAB_CLAIMED, True)
         return base[:, :wpad] if base.size(1) > wpad else base
     return None
 

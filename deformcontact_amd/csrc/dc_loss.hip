@@ -36,6 +36,7 @@ k_loss_nodes(const int32_t *__restrict__ ptr_f, const int32_t *__restrict__ oth_
         g_l1[i * 3 + 1] = sgn(dy) * inv_3n;
         g_l1[i * 3 + 2] = sgn(dz) * inv_3n;
         float gx = 0.f, gy = 0.f, gz = 0.f;
+        double gc = 0.0;      // a hub's thousands of norms: a running fp32 sum alone drifts past 1e-6 of the loss
         // in-edges src -> i:  d = (t_i - t_src) - (p_i - p_src);  d loss / d p_i = -d / |d|
         for (int q = ptr_f[i]; q < ptr_f[i + 1]; ++q) {
             const int64_t s = oth_f[q];
@@ -43,7 +44,7 @@ k_loss_nodes(const int32_t *__restrict__ ptr_f, const int32_t *__restrict__ oth_
             const float ex = (t.x - ts.x) - (p.x - ps.x), ey = (t.y - ts.y) - (p.y - ps.y),
                         ez = (t.z - ts.z) - (p.z - ps.z);
             const float nrm = sqrtf(ex * ex + ey * ey + ez * ez);
-            s_gc += nrm;
+            gc += (double)nrm;
             const float r = nrm > 0.f ? 1.f / nrm : 0.f;      // torch: zero gradient at a zero norm
             gx -= ex * r, gy -= ey * r, gz -= ez * r;
         }
@@ -57,6 +58,7 @@ k_loss_nodes(const int32_t *__restrict__ ptr_f, const int32_t *__restrict__ oth_
             const float r = nrm > 0.f ? 1.f / nrm : 0.f;
             gx += ex * r, gy += ey * r, gz += ez * r;
         }
+        s_gc = (float)gc;
         g_gcl[i * 3] = gx * inv_e;
         g_gcl[i * 3 + 1] = gy * inv_e;
         g_gcl[i * 3 + 2] = gz * inv_e;

@@ -2,8 +2,12 @@
 
 Same class names, constructor signature ``Conv(in_channels, out_channels)``, call
 ``conv(x, edge_index)`` and ``state_dict`` keys as ``torch_geometric.nn`` 2.5.2,
-which is what ``/root/reference/models/model.py:2,39,45,49,71,77`` uses.
+which is what ``/root/reference/models/model.py:2,39,45,49,71,77`` uses; and PyG's
+graph construction (``knn``, ``knn_graph``, ``radius``, ``radius_graph``,
+``/root/reference/utils/pointcloud_utils.py:7-13``) on the device search of
+``deformcontact_amd.neighbors``.
 """
+from ..neighbors import knn_graph, radius, radius_graph  # noqa: F401
 from .conv import GATConv, GCNConv, TAGConv, knn  # noqa: F401
 
-__all__ = ["TAGConv", "GCNConv", "GATConv", "knn"]
+__all__ = ["TAGConv", "GCNConv", "GATConv", "knn", "knn_graph", "radius", "radius_graph"]

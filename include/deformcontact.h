@@ -171,6 +171,34 @@ int dc_relabel_edges(const int64_t *ei, int64_t count, const int32_t *inv, int64
 int dc_gather_rows(const void *x, int64_t ldx_bytes, const int32_t *idx, void *out, int64_t ldo_bytes, int64_t n,
                    int64_t row_bytes, dc_stream_t stream);
 
+/* ---- kNN / radius neighbour search (dc_neighbors.hip; PyG knn, knn_graph, radius, radius_graph) ----
+ * dc_neighbors_fill: for every query point y[i] (fp32 [ny, >= 3], leading dimension ldy) its neighbours among the
+ *   points x[j] (fp32 [nx, >= 3], ldx) of the same graph:
+ *     batch_x [nx], batch_y [ny]: sorted int64 graph ids, or NULL for "all in graph 0";
+ *     d2 = ((dx*dx + dy*dy) + dz*dz), dx = x_j - y_i, every product and sum rounded on its own in fp32;
+ *     the candidates are ranked by (d2, j) ascending; mode DC_NEIGHBORS_KNN keeps the first `cap`,
+ *     DC_NEIGHBORS_RADIUS the first `cap` of those with d2 < r*r (r*r rounded once in fp32);
+ *     exclude_self != 0 drops j == i (by index: a duplicate point j != i stays, at distance 0).
+ *   Writes counts[i] (int32) and nbr [ny, cap] (int32, row i = the neighbours in rank order, then -1).
+ *   0 <= cap <= DC_NEIGHBORS_MAX_CAP.  The result depends on no atomic order: two calls are bit-identical.
+ *   Workspace: dc_neighbors_workspace_bytes(nx, ny) bytes, 16-byte aligned (0 when nx = 0).
+ * dc_neighbors_compact: the exact edge list of such a fill: an inclusive scan of the counts (rocPRIM) and the
+ *   scatter of row i's counts[i] neighbours to edges [offset(i), offset(i) + counts[i]) of
+ *   edge_index [2, num_edges] (int64, row length num_edges): row `query_row` gets i, the other row the neighbour.
+ *   num_edges is the counts' total, which the caller reads; edges beyond it are not written.
+ *   Workspace: dc_neighbors_compact_workspace_bytes(ny) bytes. */
+#define DC_NEIGHBORS_MAX_CAP 64
+#define DC_NEIGHBORS_KNN 0
+#define DC_NEIGHBORS_RADIUS 1
+int64_t dc_neighbors_workspace_bytes(int64_t nx, int64_t ny);
+int dc_neighbors_fill(const float *x, int64_t ldx, int64_t nx, const int64_t *batch_x, const float *y, int64_t ldy,
+                      int64_t ny, const int64_t *batch_y, int mode, float r, int cap, int exclude_self, int32_t *nbr,
+                      int32_t *counts, void *workspace, int64_t workspace_bytes, dc_stream_t stream);
+int64_t dc_neighbors_compact_workspace_bytes(int64_t ny);
+int dc_neighbors_compact(const int32_t *nbr, int cap, const int32_t *counts, int64_t ny, int query_row,
+                         int64_t *edge_index, int64_t num_edges, void *workspace, int64_t workspace_bytes,
+                         dc_stream_t stream);
+
 /* Order-dependent 64-bit content hash of an int64 device array (e.g. edge_index) into
  * out[1] (device): the key of the host's per-topology cache (loaders.TopologyCache), so a batch
  * whose edge_index has been seen before reuses its sorted adjacency. */

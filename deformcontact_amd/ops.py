@@ -1,7 +1,7 @@
 """Host-side operator layer: thin launches of the C ABI + autograd wiring.
 
 Mirrors what PyG's ``TAGConv`` / ``GCNConv`` / ``GATConv`` ``forward`` do for the
-reference (``/root/reference/models/model.py:71,77``), with every gather /
+reference (``models/model.py:71,77``), with every gather /
 scatter step executed by ``libdeformcontact_hip.so`` on the current HIP stream.
 PyTorch is used for device memory, autograd bookkeeping and (for now) the plain
 dense GEMMs.
@@ -16,16 +16,54 @@ import torch
 
 from . import _lib
 from .deferred import resolve
-from .graph import GraphIndex, SortedAdjacency, _require_cuda, current_stream_ptr
+from .graph import GraphIndex, SortedAdjacency, _require_cuda, capture_id, current_stream_ptr
 
 
-def _rowmajor(t: torch.Tensor, what: str) -> int:
-    """Return the leading dimension of a 2-D fp32 row-major (possibly column-sliced) view."""
-    if t.dim() != 2 or t.dtype != torch.float32:
-        raise ValueError(f"{what}: expected a 2-D float32 tensor, got {tuple(t.shape)} {t.dtype}")
+def _rowmajor(t: torch.Tensor, what: str, dtypes=(torch.float32,)) -> int:
+    """Return the leading dimension of a 2-D row-major (possibly column-sliced) view of one of ``dtypes``."""
+    if t.dim() != 2 or t.dtype not in dtypes:
+        raise ValueError(f"{what}: expected a 2-D tensor of {dtypes}, got {tuple(t.shape)} {t.dtype}")
     if t.size(1) > 1 and t.stride(1) != 1:
         raise ValueError(f"{what}: innermost dimension must be contiguous")
     return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
+
+
+def _vp_array(ptrs):
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+def _ptr_array(tensors):
+    return _vp_array([t.data_ptr() for t in tensors])
+
+
+def _i64_array(vals):
+    return (ctypes.c_int64 * len(vals))(*vals)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _spmm(adj: SortedAdjacency, w: Optional[torch.Tensor], x: torch.Tensor, out: Optional[torch.Tensor] = None,
+          addend: Optional[torch.Tensor] = None, rowmax: Optional[torch.Tensor] = None, rowmax_mode: int = 0):
+    """The one launch path of the fp32 hop: ``out = addend + A x`` with the edge weights ``w`` (None: ones),
+    ``dc_spmm_f32`` or its ``_rowmax`` / ``_window`` forms (``rowmax`` given / ``adj`` a row window of a merged
+    adjacency, whose operands hold only the window's rows)."""
+    n, f = x.shape
+    if out is None:
+        out = torch.empty((n, f), dtype=torch.float32, device=x.device)
+    args = [adj.ptr.data_ptr(), adj.other.data_ptr(), _ptr(w), x.data_ptr(), _rowmajor(x, "x"),
+            _ptr(addend), _rowmajor(addend, "addend") if addend is not None else 0,
+            out.data_ptr(), _rowmajor(out, "out"), n, f]
+    name = "dc_spmm_f32"
+    if rowmax is not None:
+        name += "_rowmax"
+        args += [rowmax.data_ptr(), int(rowmax_mode)]
+    if adj.row_offset:
+        name += "_window"
+        args.append(int(adj.row_offset))
+    _lib.check(getattr(_lib.lib(), name)(*args, current_stream_ptr(x.device)), name)
+    return out
 
 
 def hop(adj: SortedAdjacency, x: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -40,49 +78,13 @@ def hop(adj: SortedAdjacency, x: torch.Tensor, out: Optional[torch.Tensor] = Non
     n, f = x.shape
     if adj.ptr.numel() != n + 1:
         raise ValueError(f"hop: x has {n} rows but the graph has {adj.ptr.numel() - 1} nodes")
-    if out is None:
-        out = torch.empty((n, f), dtype=torch.float32, device=x.device)
-    ldx, ldy = _rowmajor(x, "x"), _rowmajor(out, "out")
-    if out.shape != x.shape:
+    if out is not None and out.shape != x.shape:
         raise ValueError("hop: out shape mismatch")
-    lda = 0
-    if addend is not None:
-        if addend.shape != x.shape:
-            raise ValueError("hop: addend shape mismatch")
-        lda = _rowmajor(addend, "addend")
-    w = adj.w if weighted else None
+    if addend is not None and addend.shape != x.shape:
+        raise ValueError("hop: addend shape mismatch")
     if rowmax is not None and (rowmax.dtype != torch.float32 or rowmax.numel() != n or not rowmax.is_contiguous()):
         raise ValueError("hop: rowmax must be a contiguous float32 [N] tensor")
-    if adj.row_offset:
-        # a row window of a merged adjacency: x / out / addend / rowmax hold only the window's rows
-        if rowmax is not None:
-            rc = _lib.lib().dc_spmm_f32_rowmax_window(
-                adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr() if w is not None else None,
-                x.data_ptr(), ldx, addend.data_ptr() if addend is not None else None, lda,
-                out.data_ptr(), ldy, n, f, rowmax.data_ptr(), int(rowmax_mode), int(adj.row_offset),
-                current_stream_ptr(x.device))
-            _lib.check(rc, "dc_spmm_f32_rowmax_window")
-            return out
-        rc = _lib.lib().dc_spmm_f32_window(
-            adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr() if w is not None else None,
-            x.data_ptr(), ldx, addend.data_ptr() if addend is not None else None, lda,
-            out.data_ptr(), ldy, n, f, int(adj.row_offset), current_stream_ptr(x.device))
-        _lib.check(rc, "dc_spmm_f32_window")
-        return out
-    if rowmax is not None:
-        rc = _lib.lib().dc_spmm_f32_rowmax(
-            adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr() if w is not None else None,
-            x.data_ptr(), ldx, addend.data_ptr() if addend is not None else None, lda,
-            out.data_ptr(), ldy, n, f, rowmax.data_ptr(), int(rowmax_mode),
-            current_stream_ptr(x.device))
-        _lib.check(rc, "dc_spmm_f32_rowmax")
-        return out
-    rc = _lib.lib().dc_spmm_f32(
-        adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr() if w is not None else None,
-        x.data_ptr(), ldx, addend.data_ptr() if addend is not None else None, lda,
-        out.data_ptr(), ldy, n, f, current_stream_ptr(x.device))
-    _lib.check(rc, "dc_spmm_f32")
-    return out
+    return _spmm(adj, adj.w if weighted else None, x, out, addend, rowmax, rowmax_mode)
 
 
 def weight_rowmax(ws) -> torch.Tensor:
@@ -107,14 +109,6 @@ def rowabsmax(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _rowmajor_any(t: torch.Tensor, what: str, dtypes) -> int:
-    if t.dim() != 2 or t.dtype not in dtypes:
-        raise ValueError(f"{what}: expected a 2-D tensor of {dtypes}, got {tuple(t.shape)} {t.dtype}")
-    if t.size(1) > 1 and t.stride(1) != 1:
-        raise ValueError(f"{what}: innermost dimension must be contiguous")
-    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
-
-
 def hop_bf16(adj: SortedAdjacency, x: torch.Tensor, out: Optional[torch.Tensor] = None,
              addend: Optional[torch.Tensor] = None, weighted: bool = True,
              out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
@@ -124,7 +118,7 @@ def hop_bf16(adj: SortedAdjacency, x: torch.Tensor, out: Optional[torch.Tensor] 
     _require_cuda(x, "x")
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("hop_bf16: out_dtype must be bfloat16 or float32")
-    ldx = _rowmajor_any(x, "x", (torch.bfloat16,))
+    ldx = _rowmajor(x, "x", (torch.bfloat16,))
     n, f = x.shape
     if adj.ptr.numel() != n + 1:
         raise ValueError(f"hop_bf16: x has {n} rows but the graph has {adj.ptr.numel() - 1} nodes")
@@ -132,17 +126,15 @@ def hop_bf16(adj: SortedAdjacency, x: torch.Tensor, out: Optional[torch.Tensor] 
         out = torch.empty((n, f), dtype=out_dtype, device=x.device)
     if out.shape != x.shape:
         raise ValueError("hop_bf16: out shape mismatch")
-    ldy = _rowmajor_any(out, "out", (out_dtype,))
+    ldy = _rowmajor(out, "out", (out_dtype,))
     lda = 0
     if addend is not None:
         if addend.shape != x.shape:
             raise ValueError("hop_bf16: addend shape mismatch")
-        lda = _rowmajor_any(addend, "addend", (out_dtype,))
-    w = adj.w if weighted else None
+        lda = _rowmajor(addend, "addend", (out_dtype,))
     rc = _lib.lib().dc_spmm_bf16(
-        adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr() if w is not None else None,
-        x.data_ptr(), ldx, addend.data_ptr() if addend is not None else None, lda,
-        out.data_ptr(), ldy, n, f, 1 if out_dtype == torch.float32 else 0,
+        adj.ptr.data_ptr(), adj.other.data_ptr(), _ptr(adj.w if weighted else None), x.data_ptr(), ldx,
+        _ptr(addend), lda, out.data_ptr(), ldy, n, f, 1 if out_dtype == torch.float32 else 0,
         current_stream_ptr(x.device))
     _lib.check(rc, "dc_spmm_bf16")
     return out
@@ -158,7 +150,7 @@ class _HopFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        return None, hop(ctx.g.bwd, gy.contiguous(), weighted=ctx.weighted), None
+        return None, hop(ctx.g.bwd, _grad_layout(gy, 0), weighted=ctx.weighted), None
 
 
 def propagate(g: GraphIndex, x: torch.Tensor, weighted: bool = True) -> torch.Tensor:
@@ -166,12 +158,12 @@ def propagate(g: GraphIndex, x: torch.Tensor, weighted: bool = True) -> torch.Te
     return _HopFn.apply(g, resolve(x), weighted)
 
 
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _i64_array(vals):
-    return (ctypes.c_int64 * len(vals))(*vals)
+def _grad_layout(g: torch.Tensor, row_align: int) -> torch.Tensor:
+    """The incoming gradient ``g`` in a layout the backward kernels of the calling site take, copied only if it is not
+    in one already.  ``row_align`` = 0: dense rows (plain contiguous); 1: unit inner stride, any row stride (column
+    slices pass as they are); 4: unit inner stride, and row stride and base address multiples of 4 floats (16 bytes)."""
+    ok = row_align == 1 or (row_align == 4 and g.stride(0) % 4 == 0 and g.data_ptr() % 16 == 0)
+    return g if (ok and g.stride(1) == 1) else g.contiguous()
 
 
 MAX_SEG = 4   # DC_MAX_SEG in include/deformcontact.h
@@ -202,7 +194,7 @@ DENSE_PRODUCTS = 6
 
 #: the short-reduction forward kernel for the first layers (``dc_tag_linear_fwd_narrow``: persistent, weights resident in
 #: registers, no packing launch; bit-identical to the six-product split kernel); ``DC_NARROW_FWD=0``: ``dc_tag_pack_weights`` +
-#: ``dc_tag_linear_fwd_split`` as up to round 5
+#: ``dc_tag_linear_fwd_split``
 NARROW_FWD = os.environ.get("DC_NARROW_FWD", "1") != "0"
 
 #: fp16x2 mode of the wide (Fi % 16 == 0, unconcatenated) dense blocks: two power-of-two-scaled
@@ -234,10 +226,8 @@ def hop_chain_eligible(g, adj: SortedAdjacency, slab: torch.Tensor, f: int, k: i
 
 
 #: re-form gcn_norm weights from an LDS-resident degree table inside ``dc_hop_chain_f32`` (no vector-memory loads in its
-#: hop loop) instead of loading ``w``; same bits.  False (tests): always load them.  (Round 4 kept graphs of up to
-#: 512 nodes off this form because of a rare run-to-run difference; round 5 traced that to other kernels' workgroups sharing
-#: the compute unit's LDS with a small chain workgroup and removed the condition itself - every chain workgroup now owns
-#: the whole LDS, ``dc_hopchain.hip: kChainLdsRequest`` - so the size rule is gone.)
+#: hop loop) instead of loading ``w``; same bits.  False (tests): always load them.  No size rule: every chain workgroup
+#: owns the whole LDS of its compute unit (``dc_hopchain.hip: kChainLdsRequest``).
 HOP_CHAIN_GCN = True
 
 
@@ -250,10 +240,9 @@ def hop_chain(g, adj: SortedAdjacency, slab: torch.Tensor, f: int, k: int, weigh
     # the adjacency's weights are gcn_norm's (graph.GraphIndex builds nothing else): tell the kernel so
     deg = g.fwd.ptr if (HOP_CHAIN_GCN and w is not None and g.normalize and not g.self_loops) else None
     rc = _lib.lib().dc_hop_chain_f32(
-        adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr() if w is not None else None,
-        deg.data_ptr() if deg is not None else None, adj.other.numel(),
+        adj.ptr.data_ptr(), adj.other.data_ptr(), _ptr(w), _ptr(deg), adj.other.numel(),
         nptr, nseg, slab.data_ptr(), slab.stride(0), slab.size(0), f, k, int(src_block), int(direction),
-        rowmax.data_ptr() if rowmax is not None else None, int(rowmax_mode), current_stream_ptr(slab.device))
+        _ptr(rowmax), int(rowmax_mode), current_stream_ptr(slab.device))
     _lib.check(rc, "dc_hop_chain_f32")
 
 
@@ -316,7 +305,6 @@ def _hop_cache_get(g, key, x, dev):
     cache = getattr(g, "_hop_cache", None)
     if not cache or key not in cache:
         return None
-    from .graph import capture_id
     cid = capture_id(dev)
     slab, rowmax, ecid, _ref, version = cache[key]
     if version == x._version and (ecid == cid or (cid != 0 and g._static_ok)):
@@ -325,7 +313,6 @@ def _hop_cache_get(g, key, x, dev):
 
 
 def _hop_cache_put(g, key, x, slab, rowmax, dev):
-    from .graph import capture_id
     cache = g.__dict__.setdefault("_hop_cache", {})
     if key not in cache:
         while len(cache) >= _HOP_CACHE_ENTRIES:
@@ -366,13 +353,12 @@ def _build_input_slab(g: GraphIndex, x: torch.Tensor, k: int, want_rowmax: bool,
     return slab, rowmax
 
 
-#: K = 0 layers (``dense_linear``: the ``lin`` of GCNConv / GATConv, the attention heads' Linear, the decoder) on the
-#: fp16x2 kernels too: no hop records their row maxima, so a ``dc_rowabsmax_f32`` pass over the input is added (8 us for
-#: [32768, 256]) and three MFMA products replace six.  From 128 input columns on, outputs a multiple of 16 wide
-#: (the 256 -> 3 output layer stays where it was).
-
-
 def _tag_uses_h2(fi: int, k: int, fo: Optional[int] = None) -> bool:
+    """Does a TAGConv layer of these widths run its dense blocks on the fp16x2 kernels (``DENSE_F16X2``)?  K = 0 layers
+    (``dense_linear``: the ``lin`` of GCNConv / GATConv, the attention heads' Linear, the decoder) do too: no hop
+    records their row maxima, so a ``dc_rowabsmax_f32`` pass over the input is added (8 us for [32768, 256]) and three
+    MFMA products replace six.  From 128 input columns on, outputs a multiple of 16 wide (the 256 -> 3 output layer
+    stays on the six-product split); ``fo`` None: a K = 0 layer that asked for six products."""
     concat, _, wpad = tag_slab_geometry(fi, k)
     ok = (DENSE_F16X2 and DENSE_SPLIT_BF16 and DENSE_PRODUCTS == 6 and not concat and fi % 16 == 0 and wpad % 4 == 0)
     if k >= 1:
@@ -385,11 +371,9 @@ def precompute_input_hops(g: GraphIndex, x: torch.Tensor, k: int = 3) -> None:
     will need for the no-grad input ``x`` over topology ``g`` (what ``loaders.PrefetchLoader`` does
     for the next batch while the current one trains).
 
-    (Until round 5 a ``refresh=True`` mode recomputed INTO the cached buffers of refilled static inputs.  Nothing used it,
-    and it was unsafe: re-filing an eagerly allocated slab under the id of the capture that refreshed it made the next EAGER
-    lookup miss, replace the entry and free a buffer whose address a captured graph still wrote to - a memory access
-    fault at batch 32 when round 5 tried it (``profiles/r05/j_refresh_mode_memory_fault.txt``).  Removed; refilled static inputs rebuild their
-    slabs inside the captured step, as ``bench.py`` does.)"""
+    Refilled static inputs are not refreshed in place: they rebuild their slabs inside the captured step, as ``bench.py``
+    does (recomputing INTO cached buffers freed one that a captured graph still wrote to,
+    ``profiles/r05/j_refresh_mode_memory_fault.txt``)."""
     _require_cuda(x, "x")
     if not HOP_CACHE or k < 1 or x.dtype != torch.float32 or x.dim() != 2:
         return
@@ -412,6 +396,16 @@ def _grad_sink(p):
             or g.shape != p.shape or not bucket.owns(p, g)):
         return None
     return bucket
+
+
+def _direct_sink(params, needed):
+    """The ``dp.GradBucket`` a backward kernel may accumulate the gradients of ``params`` into directly
+    (``DIRECT_PARAM_GRAD``): autograd is not recording, every one of them is ``needed`` and every ``.grad`` is a view
+    of that one bucket - else None.  The caller writes through ``p.grad`` and reports it (``note_direct_write``)."""
+    if not (DIRECT_PARAM_GRAD and not torch.is_grad_enabled() and all(needed)):
+        return None
+    sinks = [_grad_sink(p) for p in params]
+    return sinks[0] if all(s is sinks[0] for s in sinks) else None
 
 
 def tag_slab_geometry(fi: int, k: int):
@@ -477,11 +471,9 @@ def _h2_weight_prep(L, ws, k: int, fo: int, fi: int, want_t: bool, dev, st, zero
     if want_t:
         wt = torch.empty((fi, (k + 1) * fo), dtype=torch.float32, device=dev)
         wt_rowmax = torch.empty(fi, dtype=torch.float32, device=dev)
-    _lib.check(L.dc_tag_weight_prep_zero(_ptr_array(ws), k + 1, fo, fi, wmax.data_ptr(), wimg.data_ptr(),
-                                         wt.data_ptr() if wt is not None else None,
-                                         wt_rowmax.data_ptr() if wt is not None else None,
-                                         zero.data_ptr() if zero is not None else None,
-                                         zero.numel() if zero is not None else 0, st), "dc_tag_weight_prep")
+    _lib.check(L.dc_tag_weight_prep_zero(_ptr_array(ws), k + 1, fo, fi, wmax.data_ptr(), wimg.data_ptr(), _ptr(wt),
+                                         _ptr(wt_rowmax), _ptr(zero), zero.numel() if zero is not None else 0, st),
+               "dc_tag_weight_prep")
     return wmax, wimg, wt, wt_rowmax
 
 
@@ -503,15 +495,238 @@ def _dw_position(dev) -> str:
     return DW_POSITION["listed" if current_stream_ptr(dev) in DW_LAST_STREAMS else "unlisted"]
 
 
-class _TagConvFn(torch.autograd.Function):
-    """Whole TAGConv layer (+ optional fused ReLU): K hops into one ``[N, (K+1)*Fi]`` slab, then
-    ONE fp32-MFMA kernel for ``act(x W_0^T + sum_k (A^k x) W_k^T + b)`` - PyG ``tag_conv.py``
-    forward followed by ``F.relu`` (``models/model.py:71,77``).  Backward: one dW kernel
-    (+ bias grad), one dX kernel writing the per-hop gradient slab, K transposed hops.
+def _pack_weights(ws, fo: int, fi: int, wpad: int, st) -> torch.Tensor:
+    """``dc_tag_pack_weights``: the K+1 ``[Fo, Fi]`` weight blocks side by side, zero-padded to ``[Fo, wpad]``."""
+    wcat = torch.empty((fo, wpad), dtype=torch.float32, device=ws[0].device)
+    _lib.check(_lib.lib().dc_tag_pack_weights(_ptr_array(ws), len(ws), wcat.data_ptr(), fo, fi, wpad, st),
+               "dc_tag_pack_weights")
+    return wcat
 
-    Narrow layers (Fi = 21 / 25 of the input encodings) run the dense block as ONE segment
-    over the concatenated slab (K-dim (K+1)*Fi = 84 / 100: aligned float4 loads, one
-    128-wide dW tile); wide layers pass the K+1 column blocks as separate segments."""
+
+def _dense_path(fi: int, k: int, fo: int, six: bool = False, narrow_ok: bool = False) -> str:
+    """Which dense block runs a TAGConv / ``dense_linear`` layer of these widths, by the module switches as they are
+    now.  "h2": fp16x2 planes, three products, one segment over the whole slab (``six``: the layer asked to stay off
+    it).  "narrow": the short-reduction forward kernel of the first layers (``narrow_ok``: the answer of
+    ``dc_tag_linear_fwd_narrow_ok``); its backward is that of "concat".  "concat": six-product bf16 split, ONE
+    segment over the concatenated slab, zero-padded to a multiple of 16 (84 -> 96, 100 -> 112: aligned float4 loads,
+    no K tail).  "split": the same kernels with the K+1 column blocks as separate segments.  "fp32": fp32 MFMA
+    (``DENSE_SPLIT_BF16`` off), operands concatenated or not as ``tag_slab_geometry`` says."""
+    if not DENSE_SPLIT_BF16:
+        return "fp32"
+    if _tag_uses_h2(fi, k, None if six else fo):
+        return "h2"
+    if not tag_slab_geometry(fi, k)[0]:
+        return "split"
+    return "narrow" if (NARROW_FWD and DENSE_PRODUCTS == 6 and narrow_ok) else "concat"
+
+
+def _dense_operands(slab: torch.Tensor, fi: int, k: int, concat: bool):
+    """(xs, ldxs, fi_eff, nseg): a ``[N, wpad]`` slab as the segment list of the dense blocks - the whole slab as
+    one segment (``concat``) or its K+1 column blocks."""
+    ld = slab.stride(0)
+    if concat:
+        return [slab], [ld], slab.size(1), 1
+    return [slab[:, j * fi:(j + 1) * fi] for j in range(k + 1)], [ld] * (k + 1), fi, k + 1
+
+
+def _tag_slab(g, x: torch.Tensor, weights, h2: bool, need_x: bool):
+    """First step of a TAGConv layer's forward: the hop slab ``[x | A x | ... | A^K x]`` and, for the fp16x2 block
+    (``h2``), its row maxima.  -> (slab, rowmax, prepped); ``prepped``: the layer's ``_h2_weight_prep`` where it had
+    to be launched here already, else None."""
+    n, fi = x.shape
+    k = len(weights) - 1
+    dev = x.device
+    wpad = tag_slab_geometry(fi, k)[2]
+    slab = _as_slab_block0(x, n, fi, wpad)
+    if slab is None and k == 0 and wpad == fi and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        slab = x                                 # no hops: the input itself is the (1-block) slab
+    rowmax = prepped = None
+    if slab is None:
+        # the layer's own input: pack + K hops, or the cached slab when x needs no gradient
+        key = None
+        if HOP_CACHE and g is not None and k >= 1 and not need_x:
+            key = _hop_cache_key(x, k, wpad, h2)
+            hit = _hop_cache_get(g, key, x, dev)
+            if hit is not None:
+                slab, rowmax = hit
+        if slab is None:
+            slab, rowmax = _build_input_slab(g, x, k, h2)
+            if key is not None:
+                _hop_cache_put(g, key, x, slab, rowmax, dev)
+    else:
+        rowmax = torch.empty(n, dtype=torch.float32, device=dev) if h2 else None
+        zeroed = False
+        if h2 and g is not None and hop_chain_eligible(g, g.fwd, slab, fi, k):
+            # the chain launch joins its row maxima into `rowmax` with atomics: the weight preparation - one launch
+            # anyway, independent of the slab - clears it on the side (a memset node of its own: ~5 us per chain)
+            fo = weights[0].size(0)
+            prepped = _h2_weight_prep(_lib.lib(), [w.contiguous() for w in weights], k, fo, fi,
+                                      need_x and fo % 16 == 0, dev, current_stream_ptr(dev), zero=rowmax)
+            zeroed = True
+        chained_hops(g, slab, fi, k, backward=False, rowmax=rowmax, rowmax_zeroed=zeroed)
+    if h2 and k == 0:
+        rowmax = rowabsmax(slab)                 # no hop has recorded the rows' maxima: one pass over the input
+    return slab, rowmax, prepped
+
+
+def _tag_out_buffer(next_geom, n: int, fo: int, dev) -> torch.Tensor:
+    """Second step: where the layer's ``[N, Fo]`` output goes (``next_geom`` of ``tag_conv``)."""
+    if isinstance(next_geom, OutInto):
+        # rows of a buffer the caller owns (a part's rows of block 0 of a MERGED hop slab: both encoder branches
+        # feed one grouped layer)
+        out = next_geom.view
+        if out.shape != (n, fo) or out.stride(1) != 1 or out.dtype != torch.float32 or out.device != dev:
+            raise ValueError("tag_conv: out_into view has the wrong shape / layout")
+        return out
+    if next_geom is None:
+        return torch.empty((n, fo), dtype=torch.float32, device=dev)
+    # the output IS column block 0 of the next TAGConv layer's hop slab (no copy there)
+    next_width, next_wpad = next_geom
+    nxt = _alloc_slab(n, next_wpad, dev, tag=(n, fo, next_wpad))   # recognised by _as_slab_block0
+    if next_wpad > next_width:
+        nxt[:, next_width:].zero_()          # K padding of a narrow next layer
+    return nxt[:, :fo]
+
+
+def _tag_weight_gradients(ctx, slab, g: torch.Tensor, mask_ptr, ldm: int, g_rowmax=None, xrowmax=None):
+    """dW + bias gradient of a ``_TagConvFn`` layer from the gradient ``g`` (masked by the output at ``mask_ptr``
+    unless that is None) and the forward's slab: one output block per ``lins[k].weight`` in either layout of the
+    dense block.  -> (gws, gb) for autograd; all None where the kernel wrote into the parameters' bucket."""
+    k, fi, fo = ctx.k, ctx.fi, ctx.fo
+    need_ws, need_b = ctx.needs_input_grad[5:], ctx.has_bias and ctx.needs_input_grad[2]
+    gws: List[Optional[torch.Tensor]] = [None] * (k + 1)
+    if not (any(need_ws) or need_b):
+        return gws, None
+    L = _lib.lib()
+    n, dev = slab.size(0), slab.device
+    st = current_stream_ptr(dev)
+    bucket = _direct_sink(list(ctx.params) + ([ctx.bias_param] if ctx.has_bias else []),
+                          list(need_ws) + [need_b or not ctx.has_bias])
+    if bucket is not None:
+        outs = [p.grad for p in ctx.params]
+        gb_out = ctx.bias_param.grad if ctx.has_bias else None
+    else:
+        outs = [torch.empty((fo, fi), dtype=torch.float32, device=dev) for _ in range(k + 1)]
+        gb_out = torch.empty(fo, dtype=torch.float32, device=dev) if need_b else None
+    xs, ldxs, fi_eff, nseg = _dense_operands(slab, fi, k, ctx.concat)
+    nbytes = L.dc_tag_linear_bwd_dw_workspace_bytes(n, fi_eff, fo, nseg)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    args = (g.data_ptr(), g.stride(0), mask_ptr, ldm, _ptr_array(xs), _i64_array(ldxs), nseg,
+            _ptr_array(outs), k + 1, fi, _ptr(gb_out), int(bucket is not None), scratch.data_ptr(), nbytes,
+            n, fi_eff, fo)
+    if g_rowmax is not None and n % 16 == 0:
+        rc = L.dc_tag_linear_bwd_dw_h2(*args, g_rowmax.data_ptr(), xrowmax.data_ptr(), st)
+    elif ctx.path != "fp32":
+        rc = L.dc_tag_linear_bwd_dw_split(*args, DENSE_PRODUCTS, st)
+    else:
+        rc = L.dc_tag_linear_bwd_dw(*args, st)
+    _lib.check(rc, "dc_tag_linear_bwd_dw")
+    if bucket is not None:
+        bucket.note_direct_write(torch.cuda.current_stream(dev))
+        return gws, None
+    return [outs[j] if need_ws[j] else None for j in range(k + 1)], gb_out
+
+
+def _tap_h2_backward(g, fi: int, fo: int, hop_rowmax, g_rowmax, gx, gslab) -> None:
+    """The ``DEBUG_TAP`` calls of ``_tag_backward_h2`` (tools/exp/dp_flake2.py; ``HUNT_TAP_ADJ`` / ``HUNT_TAP_BIG``
+    = 1 add the adjacency arrays / the big intermediates)."""
+    DEBUG_TAP(f"bwd{fi}x{fo}.hop_rowmax", hop_rowmax)
+    DEBUG_TAP(f"bwd{fi}x{fo}.g_rowmax", g_rowmax)
+    if os.environ.get("HUNT_TAP_ADJ") == "1":
+        for nm, t in (("bwd.ptr", g.bwd.ptr), ("bwd.other", g.bwd.other), ("bwd.w", g.bwd.w), ("fwd.ptr", g.fwd.ptr)):
+            DEBUG_TAP(f"bwd{fi}x{fo}.adj.{nm}", t)
+    if os.environ.get("HUNT_TAP_BIG") == "1":
+        DEBUG_TAP(f"bwd{fi}x{fo}.gx", gx)
+        DEBUG_TAP(f"bwd{fi}x{fo}.gslab", gslab)
+
+
+def _tag_backward_h2(ctx, gout: torch.Tensor):
+    """Backward of an fp16x2 layer, in the forward's shape: gx = sum_j ((A^T)^j gm) W_j with gm = g * relu' - K
+    transposed hops on gm (which also record the row maxima), then ONE dense block with the (K+1)*Fo reduction and
+    the transposed weights.  gm and its row maxima also feed dW (no mask reads there), whose place in the sequence
+    is ``_dw_position``'s.  -> (gx, gws, gb)."""
+    slab, out, xrowmax, wt, wt_rowmax, *ws = ctx.saved_tensors
+    g, k, fi, fo = ctx.g, ctx.k, ctx.fi, ctx.fo
+    L = _lib.lib()
+    n, dev = slab.size(0), slab.device
+    st = current_stream_ptr(dev)
+    need_x = ctx.needs_input_grad[1]
+    ldm = out.stride(0) if out is not None else fo
+    gwid = (k + 1) * fo
+    gslab = _alloc_slab(n, gwid, dev)
+    gld = gslab.stride(0)
+    g_rowmax = torch.empty(n, dtype=torch.float32, device=dev)
+    hop_rowmax = torch.empty(n, dtype=torch.float32, device=dev) if need_x else None
+    # (folding this pass into the transposed chain's staging was built and measured - bit-identical, one launch and
+    # 100 MB less, and 0 - 2 % SLOWER on the step: this pass runs in the shadow of the other branch's dense blocks,
+    # the chain launch does not; tools/exp/hopchain_masked.hip keeps the kernel)
+    _lib.check(L.dc_tag_mask_grad(gout.data_ptr(), gout.stride(0), _ptr(out), ldm, gslab.data_ptr(), gld, n, fo,
+                                  g_rowmax.data_ptr(), _ptr(hop_rowmax), st), "dc_tag_mask_grad")
+
+    def weight_gradients():
+        return _tag_weight_gradients(ctx, slab, gslab, None, ldm, g_rowmax, xrowmax)
+
+    dw_pos = _dw_position(dev)
+    if not need_x:
+        return (None, *weight_gradients())
+    # dW needs gm (block 0) and the forward's slab only - not the transposed chain: "first" puts it in FRONT of chain
+    # + dX, "mid" between them, so that the two encoder branches' dW kernels do not run side by side (DW_LAST_STREAMS)
+    grads = weight_gradients() if dw_pos == "first" else None
+    chained_hops(g, gslab, fo, k, backward=False, rowmax=hop_rowmax, transposed=True, rowmax_has_block0=True)
+    if dw_pos == "mid":
+        grads = weight_gradients()
+    if wt is None:                       # forward ran without needs_input_grad
+        wt = torch.empty((fi, gwid), dtype=torch.float32, device=dev)
+        wt_rowmax = torch.empty(fi, dtype=torch.float32, device=dev)
+        _lib.check(L.dc_tag_weight_prep(_ptr_array(ws), k + 1, fo, fi, torch.empty(fo, device=dev).data_ptr(), None,
+                                        wt.data_ptr(), wt_rowmax.data_ptr(), st), "dc_tag_weight_prep")
+    gx = torch.empty((n, fi), dtype=torch.float32, device=dev)
+    rc = L.dc_tag_linear_fwd_h2p(gslab.data_ptr(), gld, wt.data_ptr(), None, 0, gx.data_ptr(), fi, n, gwid, fi,
+                                 hop_rowmax.data_ptr(), wt_rowmax.data_ptr(), None, 0, st)
+    _lib.check(rc, "dc_tag_linear_fwd_h2 (dX)")
+    if DEBUG_TAP is not None:
+        _tap_h2_backward(g, fi, fo, hop_rowmax, g_rowmax, gx, gslab)
+    if grads is None:
+        grads = weight_gradients()
+    return (gx, *grads)
+
+
+def _tag_backward_generic(ctx, gout: torch.Tensor):
+    """Backward of every other layer: one dW kernel (+ bias gradient), one dX kernel writing the per-hop gradient
+    slab, K transposed hops that fold it into block 0.  -> (gx, gws, gb)."""
+    slab, out, _, _, _, *ws = ctx.saved_tensors
+    k, fi, fo = ctx.k, ctx.fi, ctx.fo
+    L = _lib.lib()
+    n, dev = slab.size(0), slab.device
+    st = current_stream_ptr(dev)
+    mask_ptr, ldm = _ptr(out), (out.stride(0) if out is not None else fo)
+    gws, gb = _tag_weight_gradients(ctx, slab, gout, mask_ptr, ldm)
+    if not ctx.needs_input_grad[1]:
+        return None, gws, gb
+    wpad = slab.size(1)
+    if ctx.path == "narrow":
+        # the forward read the lins[k].weight matrices directly; the one-segment dX block wants them concatenated
+        ws = [_pack_weights(ws, fo, fi, wpad, st)]
+    gslab = _alloc_slab(n, wpad, dev)
+    gxs, ldgs, fi_eff, nseg = _dense_operands(gslab, fi, k, ctx.concat)
+    if ctx.path != "fp32":
+        wsb = L.dc_tag_linear_bwd_dx_split_workspace_bytes(fi_eff, fo, nseg)
+        wsx = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        rc = L.dc_tag_linear_bwd_dx_split(gout.data_ptr(), gout.stride(0), mask_ptr, ldm, _ptr_array(ws), nseg,
+                                          _ptr_array(gxs), _i64_array(ldgs), wsx.data_ptr(), wsb, n, fi_eff, fo,
+                                          DENSE_PRODUCTS, st)
+    else:
+        rc = L.dc_tag_linear_bwd_dx(gout.data_ptr(), gout.stride(0), mask_ptr, ldm, _ptr_array(ws), nseg,
+                                    _ptr_array(gxs), _i64_array(ldgs), n, fi_eff, fo, st)
+    _lib.check(rc, "dc_tag_linear_bwd_dx")
+    chained_hops(ctx.g, gslab, fi, k, backward=True)  # g_{j-1} = G_{j-1} + A^T g_j
+    return gslab[:, :fi], gws, gb
+
+
+class _TagConvFn(torch.autograd.Function):
+    """Whole TAGConv layer (+ optional fused ReLU): K hops into one ``[N, (K+1)*Fi]`` slab, then ONE dense kernel
+    (``_dense_path``) for ``act(x W_0^T + sum_k (A^k x) W_k^T + b)`` - PyG ``tag_conv.py`` forward followed by
+    ``F.relu`` (``models/model.py:71,77``).  Backward: ``_tag_backward_h2`` / ``_tag_backward_generic``."""
 
     @staticmethod
     def forward(ctx, g: GraphIndex, x: torch.Tensor, bias: Optional[torch.Tensor], relu: bool,
@@ -522,255 +737,56 @@ class _TagConvFn(torch.autograd.Function):
         if k + 1 > MAX_SEG:
             raise NotImplementedError(f"TAGConv K={k} > {MAX_SEG - 1} is not supported by the fused dense block")
         dev = x.device
-        concat, width, wpad = tag_slab_geometry(fi, k)
-        # narrow layers: one K segment over the whole slab, zero-padded to a multiple of 16 so
-        # the lean MFMA path (aligned float4 loads, no K tail) applies (84 -> 96, 100 -> 112)
-        slab = _as_slab_block0(x, n, fi, wpad)
-        if (slab is None and k == 0 and wpad == fi and x.is_contiguous() and x.data_ptr() % 16 == 0):
-            slab = x                                 # no hops: the input itself is the (1-block) slab
         L = _lib.lib()
         st = current_stream_ptr(dev)
         six = next_geom is SIX_PRODUCTS
         if six:
             next_geom = None
-        h2 = _tag_uses_h2(fi, k, None if six else fo)
-        rowmax = None
-        prepped = None
-        if slab is None:
-            # the layer's own input: pack + K hops, or the cached slab when x needs no gradient
-            key = None
-            if HOP_CACHE and g is not None and k >= 1 and not ctx.needs_input_grad[1]:
-                key = _hop_cache_key(x, k, wpad, h2)
-                hit = _hop_cache_get(g, key, x, dev)
-                if hit is not None:
-                    slab, rowmax = hit
-            if slab is None:
-                slab, rowmax = _build_input_slab(g, x, k, h2)
-                if key is not None:
-                    _hop_cache_put(g, key, x, slab, rowmax, dev)
-        else:
-            rowmax = torch.empty(n, dtype=torch.float32, device=dev) if h2 else None
-            zeroed = False
-            if h2 and g is not None and hop_chain_eligible(g, g.fwd, slab, fi, k):
-                # the chain launch joins its row maxima into `rowmax` with atomics: the weight preparation - one launch
-                # anyway, independent of the slab - clears it on the side (a memset node of its own: ~5 us per chain)
-                prepped = _h2_weight_prep(L, [w.contiguous() for w in weights], k, fo, fi,
-                                          ctx.needs_input_grad[1] and fo % 16 == 0, dev, st, zero=rowmax)
-                zeroed = True
-            chained_hops(g, slab, fi, k, backward=False, rowmax=rowmax, rowmax_zeroed=zeroed)
-        if h2 and k == 0:
-            # no hop has recorded the rows' maxima: one pass over the input
-            rowmax = torch.empty(n, dtype=torch.float32, device=dev)
-            _lib.check(L.dc_rowabsmax_f32(slab.data_ptr(), slab.stride(0), n, fi, rowmax.data_ptr(), st), "dc_rowabsmax_f32")
-        blocks = [slab[:, j * fi:(j + 1) * fi] for j in range(k + 1)]
-        narrow = (concat and NARROW_FWD and DENSE_SPLIT_BF16 and DENSE_PRODUCTS == 6
-                  and bool(L.dc_tag_linear_fwd_narrow_ok(fi, k + 1, wpad, fo)))
-        if concat and narrow:
-            # the short-reduction kernel gathers its weight fragments from the lins[k].weight matrices themselves
-            ws = [w.contiguous() for w in weights]
-            xs, ldxs, fi_eff = [slab], [slab.stride(0)], wpad
-        elif concat:
-            wc = [w.contiguous() for w in weights]
-            wcat = torch.empty((fo, wpad), dtype=torch.float32, device=dev)
-            _lib.check(L.dc_tag_pack_weights(_ptr_array(wc), k + 1, wcat.data_ptr(), fo, fi, wpad,
-                                             st), "dc_tag_pack_weights")
-            ws = [wcat]                                              # [Fo, wpad]
-            xs, ldxs, fi_eff = [slab], [slab.stride(0)], wpad
-        else:
-            ws = [w.contiguous() for w in weights]
-            xs, ldxs, fi_eff = blocks, [slab.stride(0)] * (k + 1), fi
-        if isinstance(next_geom, OutInto):
-            # the output goes into rows of a buffer the caller owns (a part's rows of block 0 of a MERGED
-            # hop slab: both encoder branches feed one grouped layer)
-            out = next_geom.view
-            if out.shape != (n, fo) or out.stride(1) != 1 or out.dtype != torch.float32 or out.device != dev:
-                raise ValueError("tag_conv: out_into view has the wrong shape / layout")
-        elif next_geom is not None:
-            # the output IS column block 0 of the next TAGConv layer's hop slab (no copy there)
-            next_width, next_wpad = next_geom
-            nxt = _alloc_slab(n, next_wpad, dev, tag=(n, fo, next_wpad))   # recognised by _as_slab_block0
-            if next_wpad > next_width:
-                nxt[:, next_width:].zero_()          # K padding of a narrow next layer
-            out = nxt[:, :fo]
-        else:
-            out = torch.empty((n, fo), dtype=torch.float32, device=dev)
+        concat, width, wpad = tag_slab_geometry(fi, k)
+        path = _dense_path(fi, k, fo, six, concat and bool(L.dc_tag_linear_fwd_narrow_ok(fi, k + 1, wpad, fo)))
+        need_x = ctx.needs_input_grad[1]
+        slab, rowmax, prepped = _tag_slab(g, x, weights, path == "h2", need_x)
+        # the short-reduction kernel gathers its weight fragments from the lins[k].weight matrices themselves
+        ws = [w.contiguous() for w in weights]
+        if concat and path != "narrow":
+            ws = [_pack_weights(ws, fo, fi, wpad, st)]
+        out = _tag_out_buffer(next_geom, n, fo, dev)
         ldo = out.stride(0)
         b = bias.contiguous() if bias is not None else None
-        args = (_ptr_array(xs), _i64_array(ldxs), _ptr_array(ws), len(xs),
-                b.data_ptr() if b is not None else None, int(relu), out.data_ptr(), ldo, n, fi_eff, fo)
-        wmax = wt = wt_rowmax = None
-        if h2:
+        wt = wt_rowmax = None
+        if path == "h2":
             # one launch: the weights scaled and split into their fp16 planes over the concatenated
             # reduction (the dense block runs as ONE segment over the whole slab and pulls them into
             # LDS by DMA), their row maxima and, when the input needs a gradient, the same for the
             # transposed weights (forward-shaped dX block)
             if prepped is None:
-                prepped = _h2_weight_prep(L, ws, k, fo, fi, ctx.needs_input_grad[1] and fo % 16 == 0, dev, st)
+                prepped = _h2_weight_prep(L, ws, k, fo, fi, need_x and fo % 16 == 0, dev, st)
             wmax, wimg, wt, wt_rowmax = prepped
-            rc = L.dc_tag_linear_fwd_h2p(slab.data_ptr(), slab.stride(0), wimg.data_ptr(),
-                                         b.data_ptr() if b is not None else None, int(relu),
-                                         out.data_ptr(), ldo, n, width, fo,
-                                         rowmax.data_ptr(), wmax.data_ptr(), None, 0, st)
-        elif narrow:
-            rc = L.dc_tag_linear_fwd_narrow(slab.data_ptr(), slab.stride(0), _ptr_array(ws), k + 1, fi,
-                                            b.data_ptr() if b is not None else None, int(relu), out.data_ptr(), ldo, n,
-                                            wpad, fo, st)
-        elif DENSE_SPLIT_BF16:
-            rc = L.dc_tag_linear_fwd_split(*args, DENSE_PRODUCTS, st)
+            rc = L.dc_tag_linear_fwd_h2p(slab.data_ptr(), slab.stride(0), wimg.data_ptr(), _ptr(b), int(relu),
+                                         out.data_ptr(), ldo, n, width, fo, rowmax.data_ptr(), wmax.data_ptr(),
+                                         None, 0, st)
+        elif path == "narrow":
+            rc = L.dc_tag_linear_fwd_narrow(slab.data_ptr(), slab.stride(0), _ptr_array(ws), k + 1, fi, _ptr(b),
+                                            int(relu), out.data_ptr(), ldo, n, wpad, fo, st)
         else:
-            rc = L.dc_tag_linear_fwd(*args, st)
+            xs, ldxs, fi_eff, nseg = _dense_operands(slab, fi, k, concat)
+            args = (_ptr_array(xs), _i64_array(ldxs), _ptr_array(ws), nseg, _ptr(b), int(relu), out.data_ptr(), ldo,
+                    n, fi_eff, fo)
+            rc = L.dc_tag_linear_fwd(*args, st) if path == "fp32" else L.dc_tag_linear_fwd_split(*args, DENSE_PRODUCTS, st)
         _lib.check(rc, "dc_tag_linear_fwd")
-        ctx.g, ctx.k, ctx.fi, ctx.fo, ctx.has_bias, ctx.relu, ctx.concat = \
-            g, k, fi, fo, bias is not None, relu, concat
-        ctx.narrow = narrow
+        ctx.g, ctx.k, ctx.fi, ctx.fo, ctx.has_bias, ctx.relu, ctx.concat, ctx.path = \
+            g, k, fi, fo, bias is not None, relu, concat, path
         ctx.params, ctx.bias_param = weights, bias       # the Parameter objects themselves
-        ctx.h2 = h2
         ctx.save_for_backward(slab, out if relu else None, rowmax, wt, wt_rowmax, *ws)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        slab, out, xrowmax, wt, wt_rowmax, *ws = ctx.saved_tensors
-        g, k, fi, fo, concat = ctx.g, ctx.k, ctx.fi, ctx.fo, ctx.concat
-        L = _lib.lib()
-        if gout.stride(1) != 1 or gout.stride(0) % 4 != 0 or gout.data_ptr() % 16 != 0:
-            gout = gout.contiguous()
-        ldg = gout.stride(0)                 # column-slice views (e.g. the dX slab) pass as is
-        n = slab.size(0)
-        dev = slab.device
-        st = current_stream_ptr(dev)
-        need_x, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        need_w = any(ctx.needs_input_grad[5:])
-        mask_ptr = out.data_ptr() if out is not None else None
-        ldm = out.stride(0) if out is not None else fo
-        wpad, lds = slab.size(1), slab.stride(0)
-        if concat:
-            xs, ldxs, fi_eff, nseg = [slab], [lds], wpad, 1
+        gout = _grad_layout(gout, 4)         # column-slice views (e.g. the dX slab) pass as is
+        if ctx.path == "h2" and ctx.fo % 16 == 0:
+            gx, gws, gb = _tag_backward_h2(ctx, gout)
         else:
-            xs = [slab[:, j * fi:(j + 1) * fi] for j in range(k + 1)]
-            ldxs, fi_eff, nseg = [lds] * (k + 1), fi, k + 1
-
-        h2 = ctx.h2
-        gws: List[Optional[torch.Tensor]] = [None] * (k + 1)
-        gb = gx = None
-        g_ptr, g_ld, g_rowmax = gout.data_ptr(), ldg, None
-
-        dw_done = not (need_w or need_b)
-
-        def weight_gradients():
-            nonlocal gws, gb
-            if need_w or need_b:
-                # one output block per lins[k].weight, in either layout of the dense block
-                sinks = [_grad_sink(p) for p in ctx.params] + \
-                    ([_grad_sink(ctx.bias_param)] if ctx.has_bias else [])
-                direct = (DIRECT_PARAM_GRAD and not torch.is_grad_enabled()
-                          and all(ctx.needs_input_grad[5:]) and (need_b or not ctx.has_bias)
-                          and sinks[0] is not None and all(b is sinks[0] for b in sinks))
-                if direct:
-                    outs = [p.grad for p in ctx.params]
-                    gb_out = ctx.bias_param.grad if ctx.has_bias else None
-                else:
-                    outs = [torch.empty((fo, fi), dtype=torch.float32, device=dev) for _ in range(k + 1)]
-                    gb_out = torch.empty(fo, dtype=torch.float32, device=dev) if need_b else None
-                nbytes = L.dc_tag_linear_bwd_dw_workspace_bytes(n, fi_eff, fo, nseg)
-                scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                args = (g_ptr, g_ld, mask_ptr, ldm, _ptr_array(xs), _i64_array(ldxs), nseg,
-                        _ptr_array(outs), k + 1, fi, gb_out.data_ptr() if gb_out is not None else None,
-                        int(direct), scratch.data_ptr(), nbytes, n, fi_eff, fo)
-                if g_rowmax is not None and n % 16 == 0:
-                    rc = L.dc_tag_linear_bwd_dw_h2(*args, g_rowmax.data_ptr(), xrowmax.data_ptr(), st)
-                elif DENSE_SPLIT_BF16:
-                    rc = L.dc_tag_linear_bwd_dw_split(*args, DENSE_PRODUCTS, st)
-                else:
-                    rc = L.dc_tag_linear_bwd_dw(*args, st)
-                _lib.check(rc, "dc_tag_linear_bwd_dw")
-                if direct:
-                    sinks[0].note_direct_write(torch.cuda.current_stream(dev))
-                else:
-                    gws = [outs[j] if ctx.needs_input_grad[5 + j] else None for j in range(k + 1)]
-                    gb = gb_out
-
-        if h2 and fo % 16 == 0 and fo % 4 == 0:
-            # fp16x2 path, backward in the forward's shape: gx = sum_j ((A^T)^j gm) W_j with
-            # gm = g * relu' - K transposed hops on gm (which also record the row maxima), then
-            # ONE dense block with the (K+1)*Fo reduction and the transposed weights.  gm and its
-            # row maxima also feed dW (no mask reads there).
-            gwid = (k + 1) * fo
-            gslab = _alloc_slab(n, gwid, dev)
-            gld = gslab.stride(0)
-            g_rowmax = torch.empty(n, dtype=torch.float32, device=dev)
-            hop_rowmax = torch.empty(n, dtype=torch.float32, device=dev) if need_x else None
-            # (folding this pass into the transposed chain's staging was built and measured in round 4 - bit-identical, one
-            # launch and 100 MB less, and 0 - 2 % SLOWER on the step: this pass runs in the shadow of the other branch's
-            # dense blocks, the chain launch does not; tools/exp/hopchain_masked.hip keeps the kernel)
-            _lib.check(L.dc_tag_mask_grad(gout.data_ptr(), ldg, mask_ptr, ldm, gslab.data_ptr(), gld, n,
-                                          fo, g_rowmax.data_ptr(),
-                                          hop_rowmax.data_ptr() if need_x else None, st),
-                       "dc_tag_mask_grad")
-            g_ptr, g_ld, mask_ptr = gslab.data_ptr(), gld, None
-            dw_pos = _dw_position(dev)
-            if need_x and dw_pos == "first":
-                # dW needs gm (block 0) and the forward's slab only - not the transposed chain: on one of the two encoder
-                # streams it goes in FRONT of chain + dX, so that the two branches' dW kernels do not run side by side
-                # (DW_LAST_STREAMS)
-                weight_gradients()
-                dw_done = True
-            if need_x:
-                chained_hops(g, gslab, fo, k, backward=False, rowmax=hop_rowmax, transposed=True,
-                             rowmax_has_block0=True)
-                if dw_pos == "mid" and not dw_done:
-                    weight_gradients()
-                    dw_done = True
-                if wt is None:                       # forward ran without needs_input_grad
-                    wt = torch.empty((fi, gwid), dtype=torch.float32, device=dev)
-                    wt_rowmax = torch.empty(fi, dtype=torch.float32, device=dev)
-                    _lib.check(L.dc_tag_weight_prep(_ptr_array(ws), k + 1, fo, fi,
-                                                    torch.empty(fo, device=dev).data_ptr(), None,
-                                                    wt.data_ptr(), wt_rowmax.data_ptr(), st),
-                               "dc_tag_weight_prep")
-                gx = torch.empty((n, fi), dtype=torch.float32, device=dev)
-                rc = L.dc_tag_linear_fwd_h2p(gslab.data_ptr(), gld, wt.data_ptr(), None, 0, gx.data_ptr(),
-                                             fi, n, gwid, fi, hop_rowmax.data_ptr(), wt_rowmax.data_ptr(),
-                                             None, 0, st)
-                _lib.check(rc, "dc_tag_linear_fwd_h2 (dX)")
-                if DEBUG_TAP is not None:
-                    DEBUG_TAP(f"bwd{fi}x{fo}.hop_rowmax", hop_rowmax)
-                    DEBUG_TAP(f"bwd{fi}x{fo}.g_rowmax", g_rowmax)
-                    if os.environ.get("HUNT_TAP_ADJ") == "1":
-                        for nm, t in (("bwd.ptr", g.bwd.ptr), ("bwd.other", g.bwd.other), ("bwd.w", g.bwd.w),
-                                      ("fwd.ptr", g.fwd.ptr)):
-                            DEBUG_TAP(f"bwd{fi}x{fo}.adj.{nm}", t)
-                    if os.environ.get("HUNT_TAP_BIG") == "1":
-                        DEBUG_TAP(f"bwd{fi}x{fo}.gx", gx)
-                        DEBUG_TAP(f"bwd{fi}x{fo}.gslab", gslab)
-                need_x = False                               # done
-
-        if not dw_done:
-            weight_gradients()
-
-        if need_x:
-            if concat and ctx.narrow:
-                # the forward read the lins[k].weight matrices directly; the one-segment dX block wants them concatenated
-                wcat = torch.empty((fo, wpad), dtype=torch.float32, device=dev)
-                _lib.check(L.dc_tag_pack_weights(_ptr_array(ws), k + 1, wcat.data_ptr(), fo, fi, wpad, st),
-                           "dc_tag_pack_weights")
-                ws = [wcat]
-            gslab = _alloc_slab(n, wpad, dev)
-            gblocks = [gslab[:, j * fi:(j + 1) * fi] for j in range(k + 1)]
-            gxs = [gslab] if concat else gblocks
-            ldxs = [gslab.stride(0)] * len(ldxs)
-            if DENSE_SPLIT_BF16:
-                wsb = L.dc_tag_linear_bwd_dx_split_workspace_bytes(fi_eff, fo, nseg)
-                wsx = torch.empty(wsb, dtype=torch.uint8, device=dev)
-                rc = L.dc_tag_linear_bwd_dx_split(g_ptr, g_ld, mask_ptr, ldm, _ptr_array(ws), nseg,
-                                                  _ptr_array(gxs), _i64_array(ldxs), wsx.data_ptr(), wsb,
-                                                  n, fi_eff, fo, DENSE_PRODUCTS, st)
-            else:
-                rc = L.dc_tag_linear_bwd_dx(g_ptr, g_ld, mask_ptr, ldm, _ptr_array(ws), nseg,
-                                            _ptr_array(gxs), _i64_array(ldxs), n, fi_eff, fo, st)
-            _lib.check(rc, "dc_tag_linear_bwd_dx")
-            chained_hops(g, gslab, fi, k, backward=True)  # g_{j-1} = G_{j-1} + A^T g_j
-            gx = gblocks[0]
+            gx, gws, gb = _tag_backward_generic(ctx, gout)
         return (None, gx, gb, None, None, *gws)
 
 
@@ -799,8 +815,6 @@ def alloc_merged_slab(mg: GraphIndex, fi: int, k: int, dev) -> torch.Tensor:
         raise ValueError("alloc_merged_slab: wide layers only (Fi a multiple of 16, (K+1)*Fi > 128)")
     n = mg.num_nodes
     slab = _alloc_slab(n, wpad, dev, tag=("merged", n, fi, wpad, tuple(mg.row_beg), tuple(mg.rows)))
-    base = slab._base if slab._base is not None else slab
-    setattr(base, _SLAB_TAG, ("merged", n, fi, wpad, tuple(mg.row_beg), tuple(mg.rows)))
     ends = list(mg.row_beg[1:]) + [n]
     for r0, rows, r1 in zip(mg.row_beg, mg.rows, ends):
         if r0 + rows < r1:
@@ -832,10 +846,6 @@ def grouped_eligible(fi: int, fo: int, k: int) -> bool:
     """Can ``tag_conv_grouped`` run a layer of these widths (the grouped kernels' shape limits)?"""
     return (_tag_uses_h2(fi, k) and fi == 256 and fo % 128 == 0 and fo % 16 == 0
             and ((k + 1) * fi) % 32 == 0 and ((k + 1) * fo) % 32 == 0)
-
-
-def _vp_array(ptrs):
-    return (ctypes.c_void_p * len(ptrs))(*ptrs)
 
 
 class _TagConvGroupedFn(torch.autograd.Function):
@@ -881,13 +891,11 @@ class _TagConvGroupedFn(torch.autograd.Function):
             wt = torch.empty((ngroups, fi, (k + 1) * fo), dtype=torch.float32, device=dev)
             wt_rowmax = torch.empty((ngroups, fi), dtype=torch.float32, device=dev)
         wcs = [[w.contiguous() for w in ws] for ws in weights]
+        wmax_p, wimg_p = _ptr_array(list(wmax)), _ptr_array(list(wimg))
         _lib.check(L.dc_tag_grouped_weight_prep(
-            _vp_array([w.data_ptr() for ws in wcs for w in ws]), ngroups, k + 1, fo, fi,
-            _vp_array([wmax[g].data_ptr() for g in range(ngroups)]),
-            _vp_array([wimg[g].data_ptr() for g in range(ngroups)]),
-            _vp_array([wt[g].data_ptr() for g in range(ngroups)]) if wt is not None else None,
-            _vp_array([wt_rowmax[g].data_ptr() for g in range(ngroups)]) if wt is not None else None, st),
-            "dc_tag_grouped_weight_prep")
+            _ptr_array([w for ws in wcs for w in ws]), ngroups, k + 1, fo, fi, wmax_p, wimg_p,
+            _ptr_array(list(wt)) if wt is not None else None,
+            _ptr_array(list(wt_rowmax)) if wt is not None else None, st), "dc_tag_grouped_weight_prep")
         if isinstance(next_geom, tuple):
             nxt = alloc_merged_slab(mg, fo, next_geom[0], dev)      # next grouped layer's slab: (K_next,)
             out = nxt[:, :fo]
@@ -896,11 +904,8 @@ class _TagConvGroupedFn(torch.autograd.Function):
         bcs = [b.contiguous() if b is not None else None for b in biases]
         row_beg, rows = _i64_array(mg.row_beg), _i64_array(mg.rows)
         _lib.check(L.dc_tag_grouped_fwd_h2p(
-            slab.data_ptr(), slab.stride(0), ngroups, row_beg, rows, n,
-            _vp_array([wimg[g].data_ptr() for g in range(ngroups)]),
-            _vp_array([b.data_ptr() if b is not None else None for b in bcs]), int(relu),
-            out.data_ptr(), out.stride(0), width, fo, rowmax.data_ptr(),
-            _vp_array([wmax[g].data_ptr() for g in range(ngroups)]), st), "dc_tag_grouped_fwd_h2p")
+            slab.data_ptr(), slab.stride(0), ngroups, row_beg, rows, n, wimg_p, _vp_array([_ptr(b) for b in bcs]),
+            int(relu), out.data_ptr(), out.stride(0), width, fo, rowmax.data_ptr(), wmax_p, st), "dc_tag_grouped_fwd_h2p")
         ctx.mg, ctx.k, ctx.fi, ctx.fo, ctx.relu, ctx.ngroups = mg, k, fi, fo, relu, ngroups
         ctx.params, ctx.bias_params = weights, biases
         ctx.save_for_backward(slab, out if relu else None, rowmax, wt, wt_rowmax)
@@ -922,19 +927,16 @@ class _TagConvGroupedFn(torch.autograd.Function):
         for g, go in enumerate(gouts):
             if go is None:
                 go = torch.zeros((mg.rows[g], fo), dtype=torch.float32, device=dev)
-            if go.stride(1) != 1 or go.stride(0) % 4 != 0 or go.data_ptr() % 16 != 0:
-                go = go.contiguous()
-            gs.append(go)
+            gs.append(_grad_layout(go, 4))
         row_beg, rows = _i64_array(mg.row_beg), _i64_array(mg.rows)
         gwid = (k + 1) * fo
         gslab = _alloc_slab(n, gwid, dev)
         g_rowmax = torch.empty(n, dtype=torch.float32, device=dev)
         hop_rowmax = torch.empty(n, dtype=torch.float32, device=dev) if need_x else None
         _lib.check(L.dc_tag_grouped_mask_grad(
-            _vp_array([t.data_ptr() for t in gs]), _i64_array([t.stride(0) for t in gs]), ngroups, row_beg, rows, n,
-            out.data_ptr() if out is not None else None, out.stride(0) if out is not None else fo,
-            gslab.data_ptr(), gslab.stride(0), fo, g_rowmax.data_ptr(),
-            hop_rowmax.data_ptr() if need_x else None, st), "dc_tag_grouped_mask_grad")
+            _ptr_array(gs), _i64_array([t.stride(0) for t in gs]), ngroups, row_beg, rows, n,
+            _ptr(out), out.stride(0) if out is not None else fo, gslab.data_ptr(), gslab.stride(0), fo,
+            g_rowmax.data_ptr(), _ptr(hop_rowmax), st), "dc_tag_grouped_mask_grad")
         gxs = [None] * ngroups
         if need_x:
             if wt is None:
@@ -944,20 +946,17 @@ class _TagConvGroupedFn(torch.autograd.Function):
             gx = torch.empty((n, fi), dtype=torch.float32, device=dev)
             _lib.check(L.dc_tag_grouped_fwd_h2p(
                 gslab.data_ptr(), gslab.stride(0), ngroups, row_beg, rows, n,
-                _vp_array([wt[g].data_ptr() for g in range(ngroups)]), None, 0, gx.data_ptr(), fi, gwid, fi,
-                hop_rowmax.data_ptr(), _vp_array([wt_rowmax[g].data_ptr() for g in range(ngroups)]), st),
-                "dc_tag_grouped_fwd_h2p (dX)")
+                _ptr_array(list(wt)), None, 0, gx.data_ptr(), fi, gwid, fi, hop_rowmax.data_ptr(),
+                _ptr_array(list(wt_rowmax)), st), "dc_tag_grouped_fwd_h2p (dX)")
             gxs = [gx[r0:r0 + r] if ctx.needs_input_grad[4 + g] else None
                    for g, (r0, r) in enumerate(zip(mg.row_beg, mg.rows))]
         pgrads = [None] * (ngroups * per)
         if need_p:
             has_bias = ctx.bias_params[0] is not None
             flat_params = [p for g in range(ngroups) for p in ([ctx.bias_params[g]] if has_bias else []) + ctx.params[g]]
-            sinks = [_grad_sink(p) for p in flat_params]
-            all_needed = all(ctx.needs_input_grad[4 + ngroups + g * per + j] for g in range(ngroups)
-                             for j in range(per) if (j > 0 or has_bias))
-            direct = (DIRECT_PARAM_GRAD and not torch.is_grad_enabled() and all_needed
-                      and sinks[0] is not None and all(b is sinks[0] for b in sinks))
+            bucket = _direct_sink(flat_params, [ctx.needs_input_grad[4 + ngroups + g * per + j] for g in range(ngroups)
+                                                for j in range(per) if (j > 0 or has_bias)])
+            direct = bucket is not None
             if direct:
                 gw_out = [[p.grad for p in ctx.params[g]] for g in range(ngroups)]
                 gb_out = [ctx.bias_params[g].grad if has_bias else None for g in range(ngroups)]
@@ -971,13 +970,11 @@ class _TagConvGroupedFn(torch.autograd.Function):
             xblocks = [slab[:, j * fi:(j + 1) * fi] for j in range(k + 1)]
             _lib.check(L.dc_tag_grouped_bwd_dw_h2(
                 gslab.data_ptr(), gslab.stride(0), _ptr_array(xblocks), _i64_array([slab.stride(0)] * (k + 1)),
-                k + 1, ngroups, row_beg, rows, n,
-                _vp_array([t.data_ptr() for ws in gw_out for t in ws]),
-                _vp_array([t.data_ptr() if t is not None else None for t in gb_out]), int(direct),
-                scratch.data_ptr(), nbytes, fi, fo, g_rowmax.data_ptr(), xrowmax.data_ptr(), st),
-                "dc_tag_grouped_bwd_dw_h2")
+                k + 1, ngroups, row_beg, rows, n, _ptr_array([t for ws in gw_out for t in ws]),
+                _vp_array([_ptr(t) for t in gb_out]), int(direct), scratch.data_ptr(), nbytes, fi, fo,
+                g_rowmax.data_ptr(), xrowmax.data_ptr(), st), "dc_tag_grouped_bwd_dw_h2")
             if direct:
-                sinks[0].note_direct_write(torch.cuda.current_stream(dev))
+                bucket.note_direct_write(torch.cuda.current_stream(dev))
             else:
                 for g in range(ngroups):
                     base = g * per
@@ -1080,9 +1077,8 @@ class _TagConvBf16Fn(torch.autograd.Function):
         else:
             out = torch.empty((n, fo), dtype=out_dtype, device=dev)
         b = bias.detach().contiguous() if bias is not None else None
-        rc = L.dc_tag_linear_fwd_bf16(slab.data_ptr(), slab.stride(0), wcat.data_ptr(),
-                                      b.data_ptr() if b is not None else None, int(relu), out.data_ptr(),
-                                      out.stride(0), int(out.dtype == torch.bfloat16), n, width, fo, st)
+        rc = L.dc_tag_linear_fwd_bf16(slab.data_ptr(), slab.stride(0), wcat.data_ptr(), _ptr(b), int(relu),
+                                      out.data_ptr(), out.stride(0), int(out.dtype == torch.bfloat16), n, width, fo, st)
         _lib.check(rc, "dc_tag_linear_fwd_bf16")
         ctx.g, ctx.k, ctx.fi, ctx.fo, ctx.relu, ctx.has_bias, ctx.x_dtype = g, k, fi, fo, relu, bias is not None, x.dtype
         ctx.save_for_backward(slab, out if relu else None, *ws)
@@ -1097,8 +1093,7 @@ class _TagConvBf16Fn(torch.autograd.Function):
         st = current_stream_ptr(dev)
         if gout.dtype not in (torch.bfloat16, torch.float32):
             gout = gout.float()
-        if gout.stride(1) != 1:
-            gout = gout.contiguous()
+        gout = _grad_layout(gout, 1)
         need_x = ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
         need_w = any(ctx.needs_input_grad[6:])
@@ -1106,7 +1101,7 @@ class _TagConvBf16Fn(torch.autograd.Function):
         gslab = _alloc_bf16(n, gwid if need_x else fo, dev)
         _lib.check(L.dc_tag_mask_grad_bf16(
             gout.data_ptr(), gout.stride(0), int(gout.dtype == torch.bfloat16),
-            out.data_ptr() if out is not None else None, out.stride(0) if out is not None else fo,
+            _ptr(out), out.stride(0) if out is not None else fo,
             int(out is not None and out.dtype == torch.bfloat16), gslab.data_ptr(), gslab.stride(0), n, fo, st),
             "dc_tag_mask_grad_bf16")
         gx = gb = None
@@ -1136,7 +1131,7 @@ class _TagConvBf16Fn(torch.autograd.Function):
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             _lib.check(L.dc_tag_linear_bwd_dw_bf16(
                 gslab.data_ptr(), gslab.stride(0), slab.data_ptr(), slab.stride(0), k + 1, _ptr_array(outs),
-                gb_out.data_ptr() if gb_out is not None else None, 0, scratch.data_ptr(), nbytes, n, fi, fo, st),
+                _ptr(gb_out), 0, scratch.data_ptr(), nbytes, n, fi, fo, st),
                 "dc_tag_linear_bwd_dw_bf16")
             gws = [outs[j] if ctx.needs_input_grad[6 + j] else None for j in range(k + 1)]
             gb = gb_out
@@ -1169,68 +1164,66 @@ def tag_conv_bf16(g: GraphIndex, x: torch.Tensor, weights, bias, relu: bool = Fa
 # --------------------------------------------------------------------------- #
 # GATConv (heads = 1): edge softmax + weighted aggregation
 # --------------------------------------------------------------------------- #
-def _spmm_w(adj: SortedAdjacency, w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    n, f = x.shape
-    out = torch.empty((n, f), dtype=torch.float32, device=x.device)
-    rc = _lib.lib().dc_spmm_f32(adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr(),
-                                x.data_ptr(), _rowmajor(x, "x"), None, 0, out.data_ptr(), f, n, f,
-                                current_stream_ptr(x.device))
-    _lib.check(rc, "dc_spmm_f32")
-    return out
+def _gat_edge_softmax(g: GraphIndex, a_src: torch.Tensor, a_dst: torch.Tensor, slope: float, n: int) -> torch.Tensor:
+    """``alpha[p] = softmax over the edges into i of leaky_relu(a_src[j] + a_dst[i])``, in ``g.fwd`` order."""
+    alpha = torch.zeros(max(g.capacity, 1), dtype=torch.float32, device=a_src.device)
+    _lib.check(_lib.lib().dc_gat_edge_softmax_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
+                                                  a_dst.data_ptr(), slope, alpha.data_ptr(), n,
+                                                  current_stream_ptr(a_src.device)), "dc_gat_edge_softmax_fwd")
+    return alpha
+
+
+def _gat_edge_backward(g: GraphIndex, gm, h, a_src, a_dst, alpha, slope: float):
+    """Backward of ``out = sum_j alpha_ij h_j`` with ``alpha`` = ``_gat_edge_softmax``, from the gradient ``gm`` of
+    ``out``: -> (gh, g_a_src, g_a_dst)."""
+    L = _lib.lib()
+    n, f = h.shape
+    dev = h.device
+    st = current_stream_ptr(dev)
+    cap = max(g.capacity, 1)
+    b2f = g.bwd_to_fwd()
+    cnt = g.fwd.ptr[-1:]
+    # d out / d h : transposed aggregation with alpha re-ordered by source
+    alpha_b = torch.zeros(cap, dtype=torch.float32, device=dev)
+    _lib.check(L.dc_gather_f32(alpha.data_ptr(), b2f.data_ptr(), alpha_b.data_ptr(), cnt.data_ptr(), g.capacity, st),
+               "dc_gather_f32")
+    gh = _spmm(g.bwd, alpha_b, gm)
+    # d out / d alpha, through the softmax, summed per source
+    galpha = torch.zeros(cap, dtype=torch.float32, device=dev)
+    _lib.check(L.dc_sddmm_f32(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), gm.data_ptr(), f, h.data_ptr(), f,
+                              galpha.data_ptr(), n, f, st), "dc_sddmm_f32")
+    ge = torch.zeros(cap, dtype=torch.float32, device=dev)
+    g_a_dst = torch.empty(n, dtype=torch.float32, device=dev)
+    _lib.check(L.dc_gat_edge_softmax_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
+                                         a_dst.data_ptr(), slope, alpha.data_ptr(), galpha.data_ptr(),
+                                         ge.data_ptr(), g_a_dst.data_ptr(), n, st), "dc_gat_edge_softmax_bwd")
+    g_a_src = torch.empty(n, dtype=torch.float32, device=dev)
+    _lib.check(L.dc_segment_sum_f32(g.bwd.ptr.data_ptr(), b2f.data_ptr(), ge.data_ptr(), g_a_src.data_ptr(), n, st),
+               "dc_segment_sum_f32")
+    return gh, g_a_src, g_a_dst
 
 
 class _GatAggregateFn(torch.autograd.Function):
+    """The unfused GATConv aggregation (edge softmax + weighted sum); ``_GatConvFn`` is the whole layer."""
+
     @staticmethod
     def forward(ctx, g: GraphIndex, h, a_src, a_dst, slope: float):
-        L = _lib.lib()
         h, a_src, a_dst = h.contiguous(), a_src.contiguous(), a_dst.contiguous()
-        n = h.size(0)
-        st = current_stream_ptr(h.device)
-        alpha = torch.zeros(max(g.capacity, 1), dtype=torch.float32, device=h.device)
-        _lib.check(L.dc_gat_edge_softmax_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(),
-                                             a_src.data_ptr(), a_dst.data_ptr(), slope,
-                                             alpha.data_ptr(), n, st), "dc_gat_edge_softmax_fwd")
-        out = _spmm_w(g.fwd, alpha, h)
+        alpha = _gat_edge_softmax(g, a_src, a_dst, slope, h.size(0))
+        out = _spmm(g.fwd, alpha, h)
         ctx.g, ctx.slope = g, slope
         ctx.save_for_backward(h, a_src, a_dst, alpha)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        L = _lib.lib()
         h, a_src, a_dst, alpha = ctx.saved_tensors
-        g, slope = ctx.g, ctx.slope
-        gout = gout.contiguous()
-        n, f = h.shape
-        dev = h.device
-        st = current_stream_ptr(dev)
-        cap = max(g.capacity, 1)
-        b2f = g.bwd_to_fwd()
-        cnt = g.fwd.ptr[-1:]
-        # d out / d h : transposed aggregation with alpha re-ordered by source
-        alpha_b = torch.zeros(cap, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_gather_f32(alpha.data_ptr(), b2f.data_ptr(), alpha_b.data_ptr(),
-                                   cnt.data_ptr(), g.capacity, st), "dc_gather_f32")
-        gh = _spmm_w(g.bwd, alpha_b, gout)
-        # d out / d alpha
-        galpha = torch.zeros(cap, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_sddmm_f32(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), gout.data_ptr(), f,
-                                  h.data_ptr(), f, galpha.data_ptr(), n, f, st), "dc_sddmm_f32")
-        ge = torch.zeros(cap, dtype=torch.float32, device=dev)
-        g_a_dst = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_gat_edge_softmax_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(),
-                                             a_src.data_ptr(), a_dst.data_ptr(), slope,
-                                             alpha.data_ptr(), galpha.data_ptr(), ge.data_ptr(),
-                                             g_a_dst.data_ptr(), n, st), "dc_gat_edge_softmax_bwd")
-        g_a_src = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_segment_sum_f32(g.bwd.ptr.data_ptr(), b2f.data_ptr(), ge.data_ptr(),
-                                        g_a_src.data_ptr(), n, st), "dc_segment_sum_f32")
+        gh, g_a_src, g_a_dst = _gat_edge_backward(ctx.g, _grad_layout(gout, 0), h, a_src, a_dst, alpha, ctx.slope)
         return None, gh, g_a_src, g_a_dst, None
 
 
 def gat_aggregate(g: GraphIndex, h, a_src, a_dst, slope: float) -> torch.Tensor:
     return _GatAggregateFn.apply(g, h, a_src, a_dst, float(slope))
-
 
 
 # --------------------------------------------------------------------------- #
@@ -1250,9 +1243,8 @@ def _agg_bias_act(adj: SortedAdjacency, w: torch.Tensor, h: torch.Tensor, bias, 
     n, f = h.shape
     y = torch.empty((n, f), dtype=torch.float32, device=h.device)
     _lib.check(_lib.lib().dc_spmm_f32_bias_act(adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr(), h.data_ptr(),
-                                               _rowmajor(h, "h"), bias.data_ptr() if bias is not None else None,
-                                               int(relu), y.data_ptr(), f, n, f, current_stream_ptr(h.device)),
-               "dc_spmm_f32_bias_act")
+                                               _rowmajor(h, "h"), _ptr(bias), int(relu), y.data_ptr(), f, n, f,
+                                               current_stream_ptr(h.device)), "dc_spmm_f32_bias_act")
     return y
 
 
@@ -1265,17 +1257,16 @@ def _mask_and_bias_grad(gy: torch.Tensor, y: Optional[torch.Tensor], bias_param,
         return gy, None
     L = _lib.lib()
     gm = torch.empty((n, f), dtype=torch.float32, device=dev) if y is not None else None
-    sink = _grad_sink(bias_param) if (need_bias and bias_param is not None) else None
-    direct = DIRECT_PARAM_GRAD and not torch.is_grad_enabled() and sink is not None
+    sink = _direct_sink([bias_param], [need_bias and bias_param is not None])
+    direct = sink is not None
     if need_bias:
         gb = bias_param.grad if direct else torch.empty(f, dtype=torch.float32, device=dev)
     else:
         gb = torch.empty(f, dtype=torch.float32, device=dev)         # (the kernel always forms it: one pass either way)
     nb = L.dc_colsum_workspace_bytes(n, f, 1)
     ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
-    _lib.check(L.dc_mask_colsum_f32(gy.data_ptr(), gy.stride(0), y.data_ptr() if y is not None else None,
-                                    y.stride(0) if y is not None else 0, gm.data_ptr() if gm is not None else None,
-                                    gm.stride(0) if gm is not None else 0, n, f, ws.data_ptr(), ws.numel(),
+    _lib.check(L.dc_mask_colsum_f32(gy.data_ptr(), gy.stride(0), _ptr(y), y.stride(0) if y is not None else 0,
+                                    _ptr(gm), gm.stride(0) if gm is not None else 0, n, f, ws.data_ptr(), ws.numel(),
                                     gb.data_ptr(), int(direct), current_stream_ptr(dev)), "dc_mask_colsum_f32")
     if direct:
         sink.note_direct_write(torch.cuda.current_stream(dev))
@@ -1298,7 +1289,7 @@ class _GcnAggFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
-        gy = gy.contiguous()
+        gy = _grad_layout(gy, 0)
         need_b = ctx.bias_param is not None and ctx.needs_input_grad[2]
         gm, gb = _mask_and_bias_grad(gy, y, ctx.bias_param, need_b)
         gh = hop(ctx.g.bwd, gm, weighted=True) if ctx.needs_input_grad[1] else None
@@ -1327,10 +1318,7 @@ class _GatConvFn(torch.autograd.Function):
         a_dst = torch.empty(n, dtype=torch.float32, device=dev)
         _lib.check(L.dc_gat_alpha_fwd(h.data_ptr(), f, a_s.data_ptr(), a_d.data_ptr(), a_src.data_ptr(),
                                       a_dst.data_ptr(), n, f, st), "dc_gat_alpha_fwd")
-        alpha = torch.zeros(max(g.capacity, 1), dtype=torch.float32, device=dev)
-        _lib.check(L.dc_gat_edge_softmax_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
-                                             a_dst.data_ptr(), slope, alpha.data_ptr(), n, st),
-                   "dc_gat_edge_softmax_fwd")
+        alpha = _gat_edge_softmax(g, a_src, a_dst, slope, n)
         y = _agg_bias_act(g.fwd, alpha, h, bias, relu)
         ctx.g, ctx.slope, ctx.relu = g, slope, relu
         ctx.params = (att_src, att_dst, bias)
@@ -1343,34 +1331,16 @@ class _GatConvFn(torch.autograd.Function):
         h, a_src, a_dst, alpha, a_s, a_d, y = ctx.saved_tensors
         g, slope = ctx.g, ctx.slope
         att_src, att_dst, bias = ctx.params
-        gy = gy.contiguous()
+        gy = _grad_layout(gy, 0)
         n, f = h.shape
         dev = h.device
         st = current_stream_ptr(dev)
         need_b = bias is not None and ctx.needs_input_grad[4]
         gm, gb = _mask_and_bias_grad(gy, y, bias, need_b)
-        cap = max(g.capacity, 1)
-        b2f = g.bwd_to_fwd()
-        cnt = g.fwd.ptr[-1:]
-        alpha_b = torch.zeros(cap, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_gather_f32(alpha.data_ptr(), b2f.data_ptr(), alpha_b.data_ptr(), cnt.data_ptr(), g.capacity, st),
-                   "dc_gather_f32")
-        gh = _spmm_w(g.bwd, alpha_b, gm)
-        galpha = torch.zeros(cap, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_sddmm_f32(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), gm.data_ptr(), f, h.data_ptr(), f,
-                                  galpha.data_ptr(), n, f, st), "dc_sddmm_f32")
-        ge = torch.zeros(cap, dtype=torch.float32, device=dev)
-        g_a_dst = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_gat_edge_softmax_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
-                                             a_dst.data_ptr(), slope, alpha.data_ptr(), galpha.data_ptr(),
-                                             ge.data_ptr(), g_a_dst.data_ptr(), n, st), "dc_gat_edge_softmax_bwd")
-        g_a_src = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_segment_sum_f32(g.bwd.ptr.data_ptr(), b2f.data_ptr(), ge.data_ptr(), g_a_src.data_ptr(), n, st),
-                   "dc_segment_sum_f32")
+        gh, g_a_src, g_a_dst = _gat_edge_backward(g, gm, h, a_src, a_dst, alpha, slope)
         # the attention dot products' backward: gh += ga_src att_src + ga_dst att_dst, the two vector gradients
-        sinks = [_grad_sink(att_src), _grad_sink(att_dst)]
-        direct = (DIRECT_PARAM_GRAD and not torch.is_grad_enabled() and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]
-                  and sinks[0] is not None and sinks[1] is sinks[0])
+        bucket = _direct_sink([att_src, att_dst], ctx.needs_input_grad[2:4])
+        direct = bucket is not None
         if direct:
             gs, gd = att_src.grad.view(-1), att_dst.grad.view(-1)
         else:
@@ -1382,7 +1352,7 @@ class _GatConvFn(torch.autograd.Function):
                                       a_d.data_ptr(), gh.data_ptr(), f, n, f, ws.data_ptr(), ws.numel(), gs.data_ptr(),
                                       gd.data_ptr(), int(direct), st), "dc_gat_alpha_bwd")
         if direct:
-            sinks[0].note_direct_write(torch.cuda.current_stream(dev))
+            bucket.note_direct_write(torch.cuda.current_stream(dev))
             gs = gd = None
         else:
             gs, gd = gs.view_as(att_src), gd.view_as(att_dst)
@@ -1391,6 +1361,7 @@ class _GatConvFn(torch.autograd.Function):
 
 def gat_conv(g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool = False) -> torch.Tensor:
     return _GatConvFn.apply(g, resolve(h), att_src, att_dst, bias, float(slope), bool(relu))
+
 
 # --------------------------------------------------------------------------- #
 # the two training losses in one pass (train.py:51-53, models/losses.py:7-19)

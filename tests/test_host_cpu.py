@@ -467,3 +467,67 @@ def test_plain_conv_call_checks_its_inputs_at_the_call_site():
     for cls in (dc.nn.GCNConv, dc.nn.GATConv):
         with pytest.raises(RuntimeError, match="HIP device"):
             cls(3, 8)(torch.zeros(2, 3), ei)
+
+
+def _narrow_ok(fi, nseg, wpad, fo):
+    """``dc_tag_linear_fwd_narrow_ok`` (dc_dense_narrow.hip), a pure host predicate: Fo = 256, Fi <= 32, a padded
+    reduction of 96 / 112 / 128."""
+    return fo == 256 and 1 <= nseg <= 4 and 1 <= fi <= 32 and nseg * fi <= wpad and wpad in (96, 112, 128)
+
+
+def _path_by_the_conditions_of_tag_conv(ops, fi, k, fo, six):
+    """The dense block a layer runs, written out as the conditions ``_TagConvFn.forward`` tested one by one before
+    ``ops._dense_path`` existed: ``h2`` first, then ``narrow``, then the split / fp32 kernels over one concatenated
+    segment or K+1 segments."""
+    concat, _, wpad = ops.tag_slab_geometry(fi, k)
+    h2 = ops._tag_uses_h2(fi, k, None if six else fo)
+    narrow = bool(concat and ops.NARROW_FWD and ops.DENSE_SPLIT_BF16 and ops.DENSE_PRODUCTS == 6
+                  and _narrow_ok(fi, k + 1, wpad, fo))
+    if h2:
+        return "h2"
+    if narrow:
+        return "narrow"
+    if not ops.DENSE_SPLIT_BF16:
+        return "fp32"
+    return "concat" if concat else "split"
+
+
+#: (Fi, K, Fo, six_products) of every layer the encoders, the attention heads and the decoder run: the TAGConv layers
+#: (K = 3), and the K = 0 shapes of ``dense_linear`` - the ``lin`` of GCNConv / GATConv (the latter with six products),
+#: the concatenated attention heads, the decoder incl. its 256 -> 3 output layer
+_LAYER_SHAPES = [(21, 3, 256, False), (25, 3, 256, False), (256, 3, 256, False),
+                 (21, 0, 256, False), (25, 0, 256, False), (256, 0, 256, False),
+                 (21, 0, 256, True), (25, 0, 256, True), (256, 0, 256, True),
+                 (256, 0, 768, False), (768, 0, 256, False), (256, 0, 3, False)]
+
+
+def test_dense_path_table(monkeypatch):
+    """``ops._dense_path``: one decision for "which dense block runs this layer".  Pinned for every layer shape of the
+    model, under the default switches (literal table) and with each switch off (against the conditions the layer
+    tested before the function existed), so that a later change of the rule is a visible change of this table."""
+    from deformcontact_amd import ops
+    for name in ("DENSE_SPLIT_BF16", "DENSE_F16X2", "NARROW_FWD"):
+        monkeypatch.setattr(ops, name, True)
+    monkeypatch.setattr(ops, "DENSE_PRODUCTS", 6)
+
+    def table():
+        return [ops._dense_path(fi, k, fo, six, _narrow_ok(fi, k + 1, ops.tag_slab_geometry(fi, k)[2], fo))
+                for fi, k, fo, six in _LAYER_SHAPES]
+
+    def expected():
+        return [_path_by_the_conditions_of_tag_conv(ops, *shape) for shape in _LAYER_SHAPES]
+    assert expected() == ["narrow", "narrow", "h2", "concat", "concat", "h2", "concat", "concat", "split",
+                          "h2", "h2", "split"]
+    assert table() == expected()
+    for name, value in (("DENSE_F16X2", False), ("NARROW_FWD", False), ("DENSE_SPLIT_BF16", False), ("DENSE_PRODUCTS", 3)):
+        with monkeypatch.context() as m:
+            m.setattr(ops, name, value)
+            assert table() == expected(), name
+            if name == "DENSE_SPLIT_BF16":
+                assert set(table()) == {"fp32"}
+            assert {"DENSE_F16X2": "h2", "NARROW_FWD": "narrow"}.get(name, "h2") not in table()
+    # the library's own predicate is the one the test spells out
+    L = _lib.lib()
+    for fi, k, fo, _ in _LAYER_SHAPES:
+        wpad = ops.tag_slab_geometry(fi, k)[2]
+        assert bool(L.dc_tag_linear_fwd_narrow_ok(fi, k + 1, wpad, fo)) == _narrow_ok(fi, k + 1, wpad, fo)

@@ -157,6 +157,18 @@ _SIGNATURES = {
     "dc_sddmm_f32": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, _vp]),
     "dc_segment_sum_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp]),
     "dc_gather_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp]),
+    "dc_gat_alpha_heads_fwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_gat_edge_softmax_heads_fwd": (c_int, [_vp, _vp, _vp, _vp, c_float, _vp, c_int64, c_int64, _vp]),
+    "dc_spmm_f32_heads_bias_act": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int, c_int, _vp, c_int64, c_int64,
+                                           c_int64, c_int64, _vp]),
+    "dc_sddmm_f32_heads": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_gat_edge_softmax_heads_bwd": (c_int, [_vp, _vp, _vp, _vp, c_float, _vp, _vp, _vp, _vp, c_int64, c_int64,
+                                              _vp]),
+    "dc_segment_sum_f32_heads": (c_int, [_vp, _vp, _vp, _vp, c_int64, c_int64, _vp]),
+    "dc_gather_f32_heads": (c_int, [_vp, _vp, _vp, _vp, c_int64, c_int64, _vp]),
+    "dc_spread_heads_f32": (c_int, [_vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
+    "dc_gat_alpha_heads_bwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, c_int64, _vp,
+                                       c_int64, _vp, _vp, c_int, _vp]),
 }
 
 

@@ -9,7 +9,7 @@ unchanged:
 * ``TAGConv``: ``lins.{0..K}.weight [out,in]`` (no per-lin bias), ``bias [out]``;
 * ``GCNConv``: ``lin.weight [out,in]`` (glorot), ``bias [out]``;
 * ``GATConv``: ``lin.weight [H*out,in]`` (glorot), ``att_src/att_dst [1,H,out]``,
-  ``bias [H*out]``.
+  ``bias [H*out]`` (``concat=False``: ``[out]``).
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -277,22 +277,27 @@ class GCNConv(nn.Module):
 
 
 class GATConv(nn.Module):
-    def __init__(self, in_channels: int, out_channels: int, heads: int = 1,
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
                  negative_slope: float = 0.2, bias: bool = True):
         super().__init__()
-        if heads != 1:
-            raise NotImplementedError("the reference only uses heads=1 (models/model.py:45,49)")
-        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        if heads < 1:
+            raise ValueError(f"heads must be >= 1, got {heads}")
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, bool(concat)
         self.negative_slope = negative_slope
         self.lin = _Lin(in_channels, heads * out_channels, initializer="glorot")
         self.lin.six_products = True             # the attention vectors' gradient cancels to 1 % of its terms: 24-bit products
         self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
         self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
         if bias:
-            self.bias = nn.Parameter(torch.zeros(heads * out_channels))
+            self.bias = nn.Parameter(torch.zeros(self.out_width))
         else:
             self.register_parameter("bias", None)
         self.reset_parameters()
+
+    @property
+    def out_width(self) -> int:
+        """Width of the output: the heads side by side (``concat``) or their mean."""
+        return self.heads * self.out_channels if self.concat else self.out_channels
 
     def reset_parameters(self):
         self.lin.reset_parameters()
@@ -313,19 +318,23 @@ class GATConv(nn.Module):
 
     def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
         """``conv(x, edge_index)`` as PyG; everything behind ``lin`` is one autograd node on fused kernels
-        (``ops.gat_conv``); ``relu=True`` also fuses the encoder's ReLU (``models/model.py:71,77``)."""
+        (``ops.gat_conv``, with several heads ``ops.gat_heads_conv``); ``relu=True`` also fuses the encoder's ReLU
+        (``models/model.py:71,77``)."""
         x = resolve(x)
         _check_inputs(x, edge_index, self.in_channels)
         if DEFER_ACTIVATION and not relu and next_conv is None:
             side = _branch_stream(self, x)
             return deferred(lambda act: _on_branch(side, lambda: self._layer(self.graph(edge_index, x.size(0)), x, act)),
-                            x.size(0), self.heads * self.out_channels, x, _grad_wanted(x, self)).guard(
+                            x.size(0), self.out_width, x, _grad_wanted(x, self)).guard(
                                 x, edge_index, *self.parameters())
         g = self.graph(edge_index, x.size(0))
         return self._layer(g, x, relu)
 
     def _layer(self, g: GraphIndex, x: Tensor, relu: bool) -> Tensor:
         h = self.lin(x)
+        if self.heads > 1:
+            return self._layer_heads(g, h, relu)
+        # one head (the mean over one head is that head: either value of ``concat``): the single-head kernels
         if ops.fused_gnn_ok(h):
             return ops.gat_conv(g, h, self.att_src, self.att_dst, self.bias, self.negative_slope, relu)
         a_src = (h * self.att_src.view(1, -1)).sum(-1)
@@ -334,6 +343,23 @@ class GATConv(nn.Module):
         if self.bias is not None:
             out = out + self.bias
         return torch.relu(out) if relu else out
+
+    def _layer_heads(self, g: GraphIndex, h: Tensor, relu: bool) -> Tensor:
+        """Several heads: the per-edge work on the kernels of dc_gat_heads.hip at every width; the row-wise passes fused
+        with it where ``ops.gat_heads_fused_ok``."""
+        nh, mean = self.heads, not self.concat
+        if ops.gat_heads_fused_ok(h, nh, mean):
+            return ops.gat_heads_conv(g, h, self.att_src, self.att_dst, self.bias, self.negative_slope, relu, nh, mean)
+        hv = h.view(-1, nh, self.out_channels)
+        a_src = (hv * self.att_src).sum(-1)
+        a_dst = (hv * self.att_dst).sum(-1)
+        out = ops.gat_heads_aggregate(g, h, a_src, a_dst, self.negative_slope, nh, mean)
+        if self.bias is not None:
+            out = out + self.bias
+        return torch.relu(out) if relu else out
+
+    def extra_repr(self) -> str:
+        return f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
 
 
 # ``models/model.py:2`` imports ``knn`` from here (it never calls it): the device search of ``neighbors``

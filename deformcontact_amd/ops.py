@@ -1364,6 +1364,207 @@ def gat_conv(g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool 
 
 
 # --------------------------------------------------------------------------- #
+# GATConv with several heads (dc_gat_heads.hip): h is [N, H*C], per-node vectors [N, H], per-edge vectors
+# [capacity, H] edge-major in g.fwd order.  One launcher per C entry.
+# --------------------------------------------------------------------------- #
+def _heads_alpha_fwd(h, a_s, a_d, nh: int, c: int):
+    """(a_src, a_dst) [N, H]: both attention dot products of every head in one pass over ``h``."""
+    n, dev = h.size(0), h.device
+    a_src = torch.empty((n, nh), dtype=torch.float32, device=dev)
+    a_dst = torch.empty((n, nh), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().dc_gat_alpha_heads_fwd(h.data_ptr(), _rowmajor(h, "h"), a_s.data_ptr(), a_d.data_ptr(),
+                                                 a_src.data_ptr(), a_dst.data_ptr(), n, nh, c, current_stream_ptr(dev)),
+               "dc_gat_alpha_heads_fwd")
+    return a_src, a_dst
+
+
+def _heads_edge_vector(g: GraphIndex, nh: int, dev) -> torch.Tensor:
+    return torch.zeros((max(g.capacity, 1), nh), dtype=torch.float32, device=dev)
+
+
+def _heads_softmax_fwd(g: GraphIndex, a_src, a_dst, slope: float, n: int, nh: int) -> torch.Tensor:
+    alpha = _heads_edge_vector(g, nh, a_src.device)
+    _lib.check(_lib.lib().dc_gat_edge_softmax_heads_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
+                                                        a_dst.data_ptr(), slope, alpha.data_ptr(), n, nh,
+                                                        current_stream_ptr(a_src.device)), "dc_gat_edge_softmax_heads_fwd")
+    return alpha
+
+
+def _heads_agg(adj: SortedAdjacency, alpha, x, bias, relu: bool, mean: bool, nh: int, c: int) -> torch.Tensor:
+    """``act(sum_p alpha[p, head] x[other[p]] + bias)`` at width H*C, or its mean over heads at width C."""
+    n, dev = x.size(0), x.device
+    y = torch.empty((n, c if mean else nh * c), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().dc_spmm_f32_heads_bias_act(adj.ptr.data_ptr(), adj.other.data_ptr(), alpha.data_ptr(),
+                                                     x.data_ptr(), _rowmajor(x, "x"), _ptr(bias), int(relu), int(mean),
+                                                     y.data_ptr(), y.size(1), n, nh, c, current_stream_ptr(dev)),
+               "dc_spmm_f32_heads_bias_act")
+    return y
+
+
+def _heads_sddmm(g: GraphIndex, gm, h, nh: int, c: int) -> torch.Tensor:
+    galpha = _heads_edge_vector(g, nh, h.device)
+    _lib.check(_lib.lib().dc_sddmm_f32_heads(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), gm.data_ptr(),
+                                             _rowmajor(gm, "gm"), h.data_ptr(), _rowmajor(h, "h"), galpha.data_ptr(),
+                                             h.size(0), nh, c, current_stream_ptr(h.device)), "dc_sddmm_f32_heads")
+    return galpha
+
+
+def _heads_softmax_bwd(g: GraphIndex, a_src, a_dst, slope: float, alpha, galpha, n: int, nh: int):
+    dev = alpha.device
+    ge = _heads_edge_vector(g, nh, dev)
+    g_a_dst = torch.empty((n, nh), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().dc_gat_edge_softmax_heads_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
+                                                        a_dst.data_ptr(), slope, alpha.data_ptr(), galpha.data_ptr(),
+                                                        ge.data_ptr(), g_a_dst.data_ptr(), n, nh,
+                                                        current_stream_ptr(dev)), "dc_gat_edge_softmax_heads_bwd")
+    return ge, g_a_dst
+
+
+def _heads_segment_sum(ptr, index_map, v, n: int, w: int) -> torch.Tensor:
+    out = torch.empty((n, w), dtype=torch.float32, device=v.device)
+    _lib.check(_lib.lib().dc_segment_sum_f32_heads(ptr.data_ptr(), _ptr(index_map), v.data_ptr(), out.data_ptr(), n, w,
+                                                   current_stream_ptr(v.device)), "dc_segment_sum_f32_heads")
+    return out
+
+
+def _heads_gather(g: GraphIndex, v, idx, w: int) -> torch.Tensor:
+    """``out[p, :] = v[idx[p], :]`` for the edges the adjacency holds (counted on the device, ``g.fwd.ptr[-1]``)."""
+    out = _heads_edge_vector(g, w, v.device)
+    _lib.check(_lib.lib().dc_gather_f32_heads(v.data_ptr(), idx.data_ptr(), out.data_ptr(), g.fwd.ptr[-1:].data_ptr(),
+                                              g.capacity, w, current_stream_ptr(v.device)), "dc_gather_f32_heads")
+    return out
+
+
+def _heads_spread(gm, nh: int, c: int) -> torch.Tensor:
+    """The gradient of the mean over heads: ``out[i, k*C + c] = gm[i, c] / H``."""
+    n, dev = gm.size(0), gm.device
+    out = torch.empty((n, nh * c), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().dc_spread_heads_f32(gm.data_ptr(), _rowmajor(gm, "gm"), out.data_ptr(), nh * c, n, nh, c,
+                                              current_stream_ptr(dev)), "dc_spread_heads_f32")
+    return out
+
+
+def _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh: int, c: int, gs, gd, accumulate: bool) -> None:
+    n, f, dev = h.size(0), nh * c, h.device
+    L = _lib.lib()
+    ws = torch.empty(max(L.dc_colsum_workspace_bytes(n, f, 2), 16), dtype=torch.uint8, device=dev)
+    _lib.check(L.dc_gat_alpha_heads_bwd(h.data_ptr(), f, g_a_src.data_ptr(), g_a_dst.data_ptr(), a_s.data_ptr(),
+                                        a_d.data_ptr(), gh.data_ptr(), f, n, nh, c, ws.data_ptr(), ws.numel(),
+                                        gs.data_ptr(), gd.data_ptr(), int(accumulate), current_stream_ptr(dev)),
+               "dc_gat_alpha_heads_bwd")
+
+
+def _gat_heads_edge_backward(g: GraphIndex, gm, h, a_src, a_dst, alpha, slope: float, nh: int, c: int):
+    """``_gat_edge_backward`` for H heads, from the gradient ``gm`` [N, H*C] of the concatenated aggregation:
+    -> (gh [N, H*C], g_a_src [N, H], g_a_dst [N, H])."""
+    n = h.size(0)
+    b2f = g.bwd_to_fwd()
+    # d out / d h : transposed aggregation with alpha re-ordered by source, H floats per edge
+    gh = _heads_agg(g.bwd, _heads_gather(g, alpha, b2f, nh), gm, None, False, False, nh, c)
+    # d out / d alpha, through the softmax, summed per source
+    galpha = _heads_sddmm(g, gm, h, nh, c)
+    ge, g_a_dst = _heads_softmax_bwd(g, a_src, a_dst, slope, alpha, galpha, n, nh)
+    return gh, _heads_segment_sum(g.bwd.ptr, b2f, ge, n, nh), g_a_dst
+
+
+class _GatHeadsAggregateFn(torch.autograd.Function):
+    """The unfused multi-head aggregation (edge softmax + weighted sum per head, concatenated or averaged over the
+    heads): the sibling of ``_GatAggregateFn``; ``_GatHeadsConvFn`` is the whole layer."""
+
+    @staticmethod
+    def forward(ctx, g: GraphIndex, h, a_src, a_dst, slope: float, nh: int, mean: bool):
+        h, a_src, a_dst = h.contiguous(), a_src.contiguous(), a_dst.contiguous()
+        c = h.size(1) // nh
+        alpha = _heads_softmax_fwd(g, a_src, a_dst, slope, h.size(0), nh)
+        out = _heads_agg(g.fwd, alpha, h, None, False, mean, nh, c)
+        ctx.g, ctx.slope, ctx.nh, ctx.c, ctx.mean = g, slope, nh, c, mean
+        ctx.save_for_backward(h, a_src, a_dst, alpha)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, a_src, a_dst, alpha = ctx.saved_tensors
+        gm = _grad_layout(gout, 0)
+        if ctx.mean:
+            gm = _heads_spread(gm, ctx.nh, ctx.c)
+        gh, g_a_src, g_a_dst = _gat_heads_edge_backward(ctx.g, gm, h, a_src, a_dst, alpha, ctx.slope, ctx.nh, ctx.c)
+        return None, gh, g_a_src, g_a_dst, None, None, None
+
+
+def gat_heads_aggregate(g: GraphIndex, h, a_src, a_dst, slope: float, heads: int, mean: bool = False) -> torch.Tensor:
+    """``h`` [N, H*C], ``a_src`` / ``a_dst`` [N, H] -> [N, H*C], or [N, C] with ``mean`` (PyG ``concat=False``)."""
+    h = resolve(h)
+    if h.dim() != 2 or heads < 1 or h.size(1) % heads or a_src.shape != (h.size(0), heads) or a_dst.shape != a_src.shape:
+        raise ValueError("gat_heads_aggregate: h must be [N, H*C] and a_src / a_dst [N, H]")
+    return _GatHeadsAggregateFn.apply(g, h, a_src, a_dst, float(slope), int(heads), bool(mean))
+
+
+def gat_heads_fused_ok(h: torch.Tensor, heads: int, mean: bool) -> bool:
+    """Widths the row-wise passes of ``gat_heads_conv`` take: ``fused_gnn_ok`` at H*C, and at C - the width of the
+    output, where the mask and the bias gradient are formed - when the heads are averaged."""
+    return fused_gnn_ok(h) and (not mean or fused_gnn_ok(h[:, :h.size(1) // heads]))
+
+
+class _GatHeadsConvFn(torch.autograd.Function):
+    """Everything of a multi-head GATConv layer behind its ``lin`` - ``_GatConvFn`` with H weights per edge: the dot
+    products of all heads in one pass over h, edge softmax, ``act(aggregation + bias)`` (concatenated, or the mean over
+    the heads) as one launch that gathers every neighbour row once; backward: mask + bias gradient in one pass, (mean:
+    the gradient spread to the heads,) transposed aggregation, SDDMM + softmax backward, and the dot products' backward
+    with the two ``[H, C]`` attention gradients in one pass."""
+
+    @staticmethod
+    def forward(ctx, g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool, nh: int, mean: bool):
+        h = h.contiguous()
+        n, f = h.shape
+        c = f // nh
+        a_s, a_d = att_src.reshape(-1).contiguous(), att_dst.reshape(-1).contiguous()
+        a_src, a_dst = _heads_alpha_fwd(h, a_s, a_d, nh, c)
+        alpha = _heads_softmax_fwd(g, a_src, a_dst, slope, n, nh)
+        y = _heads_agg(g.fwd, alpha, h, bias, relu, mean, nh, c)
+        ctx.g, ctx.slope, ctx.relu, ctx.nh, ctx.c, ctx.mean = g, slope, relu, nh, c, mean
+        ctx.params = (att_src, att_dst, bias)
+        ctx.save_for_backward(h, a_src, a_dst, alpha, a_s, a_d, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        h, a_src, a_dst, alpha, a_s, a_d, y = ctx.saved_tensors
+        g, slope, nh, c = ctx.g, ctx.slope, ctx.nh, ctx.c
+        att_src, att_dst, bias = ctx.params
+        gy = _grad_layout(gy, 0)
+        dev = h.device
+        need_b = bias is not None and ctx.needs_input_grad[4]
+        gm, gb = _mask_and_bias_grad(gy, y, bias, need_b)
+        if ctx.mean:
+            gm = _heads_spread(gm, nh, c)
+        gh, g_a_src, g_a_dst = _gat_heads_edge_backward(g, gm, h, a_src, a_dst, alpha, slope, nh, c)
+        # the attention dot products' backward: gh += ga_src att_src + ga_dst att_dst per head, the two [H, C] gradients
+        bucket = _direct_sink([att_src, att_dst], ctx.needs_input_grad[2:4])
+        direct = bucket is not None
+        if direct:
+            gs, gd = att_src.grad.view(-1), att_dst.grad.view(-1)
+        else:
+            gs = torch.empty(nh * c, dtype=torch.float32, device=dev)
+            gd = torch.empty(nh * c, dtype=torch.float32, device=dev)
+        _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh, c, gs, gd, direct)
+        if direct:
+            bucket.note_direct_write(torch.cuda.current_stream(dev))
+            gs = gd = None
+        else:
+            gs, gd = gs.view_as(att_src), gd.view_as(att_dst)
+        return None, gh, gs, gd, gb, None, None, None, None
+
+
+def gat_heads_conv(g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool = False, heads: int = 1,
+                   mean: bool = False) -> torch.Tensor:
+    """The layer behind ``lin`` for ``heads`` >= 1 (``h`` [N, H*C], ``att_*`` [1, H, C]; ``gat_heads_fused_ok``)."""
+    h = resolve(h)
+    if h.dim() != 2 or heads < 1 or h.size(1) != att_src.numel() or att_src.numel() % heads:
+        raise ValueError("gat_heads_conv: h must be [N, H*C] and att_src / att_dst [1, H, C]")
+    return _GatHeadsConvFn.apply(g, h, att_src, att_dst, bias, float(slope), bool(relu), int(heads), bool(mean))
+
+
+# --------------------------------------------------------------------------- #
 # the two training losses in one pass (train.py:51-53, models/losses.py:7-19)
 # --------------------------------------------------------------------------- #
 class _ContactLossFn(torch.autograd.Function):

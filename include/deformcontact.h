@@ -633,6 +633,57 @@ int dc_segment_sum_f32(const int32_t *ptr, const int32_t *map, const float *v, f
 int dc_gather_f32(const float *v, const int32_t *idx, float *out, const int32_t *count_ptr,
                   int64_t cap, dc_stream_t stream);
 
+/* ---- GATConv with H attention heads (heads > 1; concat or mean over heads) (dc_gat_heads.hip) ----
+ * PyG gat_conv.py with h = lin(x) viewed as [N, H, C].  The entries above carry one scalar per edge and
+ * per node; these carry H, EDGE-MAJOR: a_src / a_dst / g_a_src / g_a_dst are [N, H] row-major, alpha /
+ * galpha / ge are [capacity, H] in key_row=1 order - the H values of an edge sit together, so one read
+ * of other[p] and of the segment bounds serves every head and a neighbour row of H*C floats is gathered
+ * once.  Any H >= 1, C >= 1 and in-degree; sums in p order, no float atomics (deterministic).
+ *   dc_gat_alpha_heads_fwd        : a_src[i,k] = h[i,kC:(k+1)C] . att_src[kC:(k+1)C], a_dst likewise (att_*
+ *                                   are the [1,H,C] parameters, flat), one pass over h
+ *   dc_gat_edge_softmax_heads_fwd : alpha[p,k] = softmax over segment i of leaky_relu(a_src[other[p],k] +
+ *                                   a_dst[i,k]), denominator + 1e-16; per head the arithmetic of
+ *                                   dc_gat_edge_softmax_fwd
+ *   dc_spmm_f32_heads_bias_act    : y[i,c] = act(sum_p alpha[p,c/C] x[other[p],c] + bias[c]) over the H*C
+ *                                   columns; mean != 0: y[i,c] = act((sum_k sum_p alpha[p,k] x[other[p],kC+c]) / H
+ *                                   + bias[c]) over C columns.  Sum from zero in p order, bias added to the
+ *                                   finished sum (bias may be NULL, relu 0/1); 16-byte loads when C % 4 == 0
+ *                                   and rows are 16-byte aligned.  On the key_row=0 set with alpha re-ordered by
+ *                                   source (dc_gather_f32_heads) it is the transposed aggregation of the backward.
+ *   dc_sddmm_f32_heads            : d[p,k] = <g[i,kC:(k+1)C], h[other[p],kC:(k+1)C]>, each h row read once
+ *   dc_gat_edge_softmax_heads_bwd : ge[p,k] and g_a_dst[i,k] = sum over segment i of ge[p,k], as
+ *                                   dc_gat_edge_softmax_bwd per head
+ *   dc_segment_sum_f32_heads      : out[i,k] = sum over p in segment i of v[map ? map[p] : p, k], rows of W floats
+ *   dc_gather_f32_heads           : out[p,:] = v[idx[p],:] for p < *count_ptr, rows of W floats
+ *   dc_spread_heads_f32           : out[i,kC+c] = g[i,c] / H (the gradient of the mean over heads)
+ *   dc_gat_alpha_heads_bwd        : gh[i,c] += ga_src[i,c/C] att_src[c] + ga_dst[i,c/C] att_dst[c], g_att_src[c]
+ *                                   (+)= sum_i ga_src[i,c/C] h[i,c], g_att_dst likewise, per-block partials
+ *                                   combined in block order; H*C % 4 == 0 with H*C/4 dividing 256, 16-byte
+ *                                   aligned rows, workspace of dc_colsum_workspace_bytes(N, H*C, 2) */
+int dc_gat_alpha_heads_fwd(const float *h, int64_t ldh, const float *att_src, const float *att_dst,
+                           float *a_src, float *a_dst, int64_t N, int64_t H, int64_t C, dc_stream_t stream);
+int dc_gat_edge_softmax_heads_fwd(const int32_t *ptr, const int32_t *other, const float *a_src,
+                                  const float *a_dst, float slope, float *alpha, int64_t N, int64_t H,
+                                  dc_stream_t stream);
+int dc_spmm_f32_heads_bias_act(const int32_t *ptr, const int32_t *other, const float *alpha, const float *x,
+                               int64_t ldx, const float *bias, int relu, int mean, float *y, int64_t ldy,
+                               int64_t N, int64_t H, int64_t C, dc_stream_t stream);
+int dc_sddmm_f32_heads(const int32_t *ptr, const int32_t *other, const float *g, int64_t ldg, const float *h,
+                       int64_t ldh, float *d, int64_t N, int64_t H, int64_t C, dc_stream_t stream);
+int dc_gat_edge_softmax_heads_bwd(const int32_t *ptr, const int32_t *other, const float *a_src,
+                                  const float *a_dst, float slope, const float *alpha, const float *galpha,
+                                  float *ge, float *g_a_dst, int64_t N, int64_t H, dc_stream_t stream);
+int dc_segment_sum_f32_heads(const int32_t *ptr, const int32_t *map, const float *v, float *out, int64_t N,
+                             int64_t W, dc_stream_t stream);
+int dc_gather_f32_heads(const float *v, const int32_t *idx, float *out, const int32_t *count_ptr, int64_t cap,
+                        int64_t W, dc_stream_t stream);
+int dc_spread_heads_f32(const float *g, int64_t ldg, float *out, int64_t ldo, int64_t N, int64_t H, int64_t C,
+                        dc_stream_t stream);
+int dc_gat_alpha_heads_bwd(const float *h, int64_t ldh, const float *ga_src, const float *ga_dst,
+                           const float *att_src, const float *att_dst, float *gh, int64_t ldgh, int64_t N,
+                           int64_t H, int64_t C, void *workspace, int64_t workspace_bytes, float *g_att_src,
+                           float *g_att_dst, int accumulate, dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

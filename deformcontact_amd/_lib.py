@@ -32,6 +32,8 @@ _SIGNATURES = {
     "dc_graph_build_plan": (c_int, [c_int64, c_int64, c_int, POINTER(c_int), POINTER(c_int)]),
     "dc_graph_build_segmented": (c_int, [_vp, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), c_int,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dc_graph_build_segmented_loops": (c_int, [_vp, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), c_int,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dc_attn_flash_prep": (c_int, [_vp, c_int64, c_int64, _vp, _vp, _vp]),
     "dc_attn_flash_ds": (c_int, [_vp, c_int64, _vp, _vp, c_int64, _vp, _vp, _vp, _vp, _vp, _vp, c_int64, c_int64,
                                  c_int64, c_int64, _vp, _vp, c_int64, _vp, _vp, _vp, _vp]),
@@ -169,6 +171,14 @@ _SIGNATURES = {
     "dc_spread_heads_f32": (c_int, [_vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
     "dc_gat_alpha_heads_bwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, c_int64, _vp,
                                        c_int64, _vp, _vp, c_int, _vp]),
+    "dc_gat_edge_attr_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int, c_float, _vp, _vp, c_int64, c_int64, c_int64,
+                                     c_int64, _vp]),
+    "dc_gat_edge_attr_softmax_fwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_float, _vp, c_int64, c_int64, _vp]),
+    "dc_gat_edge_attr_softmax_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_float, _vp, _vp, _vp, _vp, c_int64, c_int64,
+                                             _vp]),
+    "dc_gat_edge_attr_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "dc_gat_edge_attr_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, _vp, c_int, _vp, c_int64, _vp, c_int64, c_int64,
+                                     c_int64, c_int64, c_int64, _vp, c_int64, _vp]),
 }
 
 

@@ -548,6 +548,101 @@ k_build_segment(SegBuild b) {
     }
 }
 
+// The self_loops = 1 form (GCNConv / GATConv adjacencies: input self loops dropped, one loop per node appended with edge id
+// E + node, last in its group).  How many edges the earlier graphs keep is data, not layout: every workgroup counts the
+// self loops among the input edges in front of its graph itself (a read of at most 16 E bytes through L2) - still one
+// launch, no workspace, no cross-workgroup order.  Graph g then writes from slot edge_ptr[g] - loops in front + node_ptr[g]:
+// group i holds its kept edges in input order, then the loop.  An edge that leaves its graph is flagged and placed on
+// node 0 as an ordinary edge (the counts of every later graph stay those of the raw src == dst test); gcn_norm degrees
+// count the loop.  The arrays up to ptr[N] are those of dc_graph_build(self_loops = 1), bit for bit.
+constexpr uint16_t kSegDropped = 0xffff;      // (node ids of a graph are < kSegNodes = 4096)
+
+__global__ void __launch_bounds__(1024)
+k_build_segment_loops(SegBuild b) {
+    __shared__ uint16_t key16[kSegEdges], oth16[kSegEdges], tmp[kSegEdges];
+    __shared__ int32_t excl[kSegNodes + 4], cur[kSegNodes], degin[kSegNodes];
+    __shared__ int32_t dropped_before;
+    const int seg = blockIdx.x, side = blockIdx.y, tid = threadIdx.x;   // side 0: by destination, 1: by source
+    const int n0 = b.node_ptr[seg], e0 = b.edge_ptr[seg];
+    const int nn = b.node_ptr[seg + 1] - n0, ne = b.edge_ptr[seg + 1] - e0;
+    for (int i = tid; i < nn; i += 1024) cur[i] = 0, degin[i] = 1;      // (the loop is an in-edge)
+    if (tid == 0) dropped_before = 0;
+    __syncthreads();
+    int loops = 0;
+    for (int e = tid; e < e0; e += 1024) loops += b.src[e] == b.dst[e];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) loops += __shfl_xor(loops, o);
+    if ((tid & 63) == 0 && loops) atomicAdd(&dropped_before, loops);
+    bool bad = false;
+    const int64_t *__restrict__ gs = b.src + e0, *__restrict__ gd = b.dst + e0;
+    for (int e = tid; e < ne; e += 1024) {
+        const int64_t sv = gs[e], dv = gd[e];
+        if (sv == dv) {                                 // dropped; outside its graph's range: flagged as any endpoint is
+            if (sv < n0 || sv >= n0 + nn) bad = true;
+            key16[e] = kSegDropped;
+            continue;
+        }
+        int64_t s = sv - n0, d = dv - n0;
+        if (s < 0 || s >= nn || d < 0 || d >= nn) bad = true, s = d = 0;
+        const int k = (int)(side ? s : d), o = (int)(side ? d : s);
+        key16[e] = (uint16_t)k, oth16[e] = (uint16_t)o;
+        atomicAdd(&cur[k], 1);
+        if (side) atomicAdd(&degin[d], 1);
+    }
+    if (bad) atomicOr(b.status, 1);
+    __syncthreads();
+    const int base = e0 - dropped_before + n0;          // first output slot of this graph
+    int v[4], sum = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = 4 * tid + j;
+        v[j] = i < nn ? cur[i] : 0;
+        sum += v[j];
+    }
+    int total;
+    int run = block_incl_scan<16>(sum, &total) - sum;
+    int32_t *__restrict__ ptr = b.ptr[side];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = 4 * tid + j;
+        if (i < nn) {
+            excl[i] = run, cur[i] = run;
+            if (!side) degin[i] = v[j] + 1;
+            ptr[n0 + i] = base + run + i;
+        }
+        run += v[j];
+    }
+    if (tid == 0) {
+        excl[nn] = total;
+        if (b.last && seg == b.nseg - 1) ptr[b.N] = base + total + nn;
+    }
+    __syncthreads();
+    for (int e = tid; e < ne; e += 1024)
+        if (key16[e] != kSegDropped) tmp[atomicAdd(&cur[key16[e]], 1)] = (uint16_t)e;
+    __syncthreads();
+    int32_t *__restrict__ other = b.other[side], *__restrict__ perm = b.perm[side];
+    float *__restrict__ w = b.w[side];
+    for (int p = tid; p < total; p += 1024) {
+        const int e = tmp[p], k = key16[e], o = oth16[e];
+        const int beg = excl[k], end = excl[k + 1];
+        int rank = 0;
+        for (int q = beg; q < end; ++q) rank += tmp[q] < e;
+        const int64_t out = (int64_t)base + beg + k + rank;
+        perm[out] = e0 + e;
+        other[out] = n0 + o;
+        if (w) {
+            const int sl = side ? k : o, dl = side ? o : k;
+            w[out] = inv_sqrt_count(degin[sl]) * 1.0f * inv_sqrt_count(degin[dl]);
+        }
+    }
+    for (int i = tid; i < nn; i += 1024) {              // the appended loops: last in their groups
+        const int64_t out = (int64_t)base + excl[i + 1] + i;
+        perm[out] = (int32_t)(b.E + n0 + i);
+        other[out] = n0 + i;
+        if (w) w[out] = inv_sqrt_count(degin[i]) * 1.0f * inv_sqrt_count(degin[i]);
+    }
+}
+
 __global__ void __launch_bounds__(256)
 k_invert_perm(const int32_t *perm, const int32_t *n_ptr, int32_t *pos_of, int64_t max_edges) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1123,11 +1218,11 @@ extern "C" int dc_graph_build_parts(const int64_t *const *edge_index_parts, cons
     return run_build(b, 2, stream, "dc_graph_build_parts");
 }
 
-extern "C" int dc_graph_build_segmented(const int64_t *edge_index, int64_t E, int64_t N,
-                                        const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
-                                        int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
-                                        int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
-                                        int32_t *status, dc_stream_t stream_) {
+static int build_segmented(int self_loops, const int64_t *edge_index, int64_t E, int64_t N,
+                           const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                           int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
+                           int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
+                           int32_t *status, dc_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     DC_REQUIRE(E > 0 && N > 0 && nseg >= 1, "dc_graph_build_segmented: needs E > 0, N > 0 and >= 1 graph");
     DC_REQUIRE(E + N < (int64_t)INT32_MAX, "dc_graph_build_segmented: E+N=%lld exceeds int32 indexing",
@@ -1160,9 +1255,28 @@ extern "C" int dc_graph_build_segmented(const int64_t *edge_index, int64_t E, in
             b.edge_ptr[i] = (int32_t)edge_ptr_host[first + i];
         }
         b.nseg = cnt, b.last = first + cnt == nseg;
-        DC_LAUNCH(k_build_segment, dim3((unsigned)cnt, 2), dim3(1024), 0, stream, b);
+        if (self_loops) DC_LAUNCH(k_build_segment_loops, dim3((unsigned)cnt, 2), dim3(1024), 0, stream, b);
+        else DC_LAUNCH(k_build_segment, dim3((unsigned)cnt, 2), dim3(1024), 0, stream, b);
     }
     return check_launch("dc_graph_build_segmented");
+}
+
+extern "C" int dc_graph_build_segmented(const int64_t *edge_index, int64_t E, int64_t N,
+                                        const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                                        int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
+                                        int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
+                                        int32_t *status, dc_stream_t stream) {
+    return build_segmented(0, edge_index, E, N, node_ptr_host, edge_ptr_host, nseg, ptr_f, other_f, perm_f, w_f, ptr_b,
+                           other_b, perm_b, w_b, status, stream);
+}
+
+extern "C" int dc_graph_build_segmented_loops(const int64_t *edge_index, int64_t E, int64_t N,
+                                              const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                                              int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
+                                              int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
+                                              int32_t *status, dc_stream_t stream) {
+    return build_segmented(1, edge_index, E, N, node_ptr_host, edge_ptr_host, nseg, ptr_f, other_f, perm_f, w_f, ptr_b,
+                           other_b, perm_b, w_b, status, stream);
 }
 
 extern "C" int dc_invert_perm(const int32_t *perm, const int32_t *ptr_last, int32_t *pos_of,

@@ -43,11 +43,20 @@ __device__ __forceinline__ float subh_sum(float v) {
     return v;
 }
 
-template <int HB>
+// EDGE (GATConv(edge_dim=...), dc_gat_edge.hip): the logit carries a third, per-edge addend a_edge[p, k] - added to the
+// finished a_src + a_dst, so an a_edge of zeros leaves every bit as it is; EDGE = false is the code without the operand.
+template <bool EDGE>
+__device__ __forceinline__ float logit_h(float as, float ad, const float *__restrict__ ae, int b) {
+    const float s = as + ad;
+    if constexpr (EDGE) return s + ae[b];
+    else return s;
+}
+
+template <int HB, bool EDGE = false>
 __global__ void __launch_bounds__(256)
 k_gat_softmax_heads_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
                         const float *__restrict__ a_src, const float *__restrict__ a_dst, float slope,
-                        float *__restrict__ alpha, int64_t N, int H) {
+                        float *__restrict__ alpha, int64_t N, int H, const float *__restrict__ a_edge) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kSubH;
     const int sub = threadIdx.x % kSubH;
     const bool live = i < N;
@@ -62,19 +71,21 @@ k_gat_softmax_heads_fwd(const int32_t *__restrict__ ptr, const int32_t *__restri
         }
         for (int p = beg + sub; p < end; p += kSubH) {
             const float *as = a_src + (int64_t)other[p] * H + k0;
+            const float *ae = EDGE ? a_edge + (int64_t)p * H + k0 : nullptr;
 #pragma unroll
             for (int b = 0; b < HB; ++b)
-                if (k0 + b < H) m[b] = fmaxf(m[b], lrelu_h(as[b] + ad[b], slope));
+                if (k0 + b < H) m[b] = fmaxf(m[b], lrelu_h(logit_h<EDGE>(as[b], ad[b], ae, b), slope));
         }
 #pragma unroll
         for (int b = 0; b < HB; ++b) m[b] = subh_max(m[b]);
         for (int p = beg + sub; p < end; p += kSubH) {
             const float *as = a_src + (int64_t)other[p] * H + k0;
+            const float *ae = EDGE ? a_edge + (int64_t)p * H + k0 : nullptr;
             float *al = alpha + (int64_t)p * H + k0;
 #pragma unroll
             for (int b = 0; b < HB; ++b)
                 if (k0 + b < H) {
-                    const float ex = expf(lrelu_h(as[b] + ad[b], slope) - m[b]);
+                    const float ex = expf(lrelu_h(logit_h<EDGE>(as[b], ad[b], ae, b), slope) - m[b]);
                     al[b] = ex;
                     s[b] += ex;
                 }
@@ -90,12 +101,13 @@ k_gat_softmax_heads_fwd(const int32_t *__restrict__ ptr, const int32_t *__restri
     }
 }
 
-template <int HB>
+template <int HB, bool EDGE = false>
 __global__ void __launch_bounds__(256)
 k_gat_softmax_heads_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
                         const float *__restrict__ a_src, const float *__restrict__ a_dst, float slope,
                         const float *__restrict__ alpha, const float *__restrict__ galpha,
-                        float *__restrict__ ge, float *__restrict__ g_a_dst, int64_t N, int H) {
+                        float *__restrict__ ge, float *__restrict__ g_a_dst, int64_t N, int H,
+                        const float *__restrict__ a_edge) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kSubH;
     const int sub = threadIdx.x % kSubH;
     const bool live = i < N;
@@ -119,11 +131,12 @@ k_gat_softmax_heads_bwd(const int32_t *__restrict__ ptr, const int32_t *__restri
         for (int p = beg + sub; p < end; p += kSubH) {
             const float *as = a_src + (int64_t)other[p] * H + k0;
             const float *al = alpha + (int64_t)p * H + k0, *ga = galpha + (int64_t)p * H + k0;
+            const float *ae = EDGE ? a_edge + (int64_t)p * H + k0 : nullptr;
             float *o = ge + (int64_t)p * H + k0;
 #pragma unroll
             for (int b = 0; b < HB; ++b)
                 if (k0 + b < H) {
-                    const float s = as[b] + ad[b];
+                    const float s = logit_h<EDGE>(as[b], ad[b], ae, b);
                     const float g = al[b] * (ga[b] - dot[b]) * (s > 0.f ? 1.0f : slope);
                     o[b] = g;
                     acc[b] += g;
@@ -454,6 +467,14 @@ using namespace dc;
         else if ((H) <= 4) DC_LAUNCH((kernel<4>), grid, dim3(256), 0, stream, __VA_ARGS__);              \
         else DC_LAUNCH((kernel<8>), grid, dim3(256), 0, stream, __VA_ARGS__);                            \
     } while (0)
+// ... with the per-edge addend of the logit (GATConv(edge_dim=...))
+#define DC_HEADS_HB_EDGE(kernel, H, grid, stream, ...)                                                  \
+    do {                                                                                                 \
+        if ((H) == 1) DC_LAUNCH((kernel<1, true>), grid, dim3(256), 0, stream, __VA_ARGS__);             \
+        else if ((H) == 2) DC_LAUNCH((kernel<2, true>), grid, dim3(256), 0, stream, __VA_ARGS__);        \
+        else if ((H) <= 4) DC_LAUNCH((kernel<4, true>), grid, dim3(256), 0, stream, __VA_ARGS__);        \
+        else DC_LAUNCH((kernel<8, true>), grid, dim3(256), 0, stream, __VA_ARGS__);                      \
+    } while (0)
 
 extern "C" int dc_gat_alpha_heads_fwd(const float *h, int64_t ldh, const float *att_src, const float *att_dst,
                                       float *a_src, float *a_dst, int64_t N, int64_t H, int64_t C, dc_stream_t stream_) {
@@ -481,8 +502,37 @@ extern "C" int dc_gat_edge_softmax_heads_fwd(const int32_t *ptr, const int32_t *
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && a_src && a_dst && alpha, "dc_gat_edge_softmax_heads_fwd: null pointer");
     const dim3 grid((unsigned)((N * kSubH + 255) / 256));
-    DC_HEADS_HB(k_gat_softmax_heads_fwd, H, grid, stream, ptr, other, a_src, a_dst, slope, alpha, N, (int)H);
+    DC_HEADS_HB(k_gat_softmax_heads_fwd, H, grid, stream, ptr, other, a_src, a_dst, slope, alpha, N, (int)H,
+                (const float *)nullptr);
     return check_launch("dc_gat_edge_softmax_heads_fwd");
+}
+
+// the two entries of GATConv(edge_dim=...) that share the kernel templates above (the rest: dc_gat_edge.hip)
+extern "C" int dc_gat_edge_attr_softmax_fwd(const int32_t *ptr, const int32_t *other, const float *a_src,
+                                            const float *a_dst, const float *a_edge, float slope, float *alpha,
+                                            int64_t N, int64_t H, dc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DC_HEADS_SHAPE("dc_gat_edge_attr_softmax_fwd", N, H, 1);
+    if (N == 0) return DC_OK;
+    DC_REQUIRE(ptr && other && a_src && a_dst && a_edge && alpha, "dc_gat_edge_attr_softmax_fwd: null pointer");
+    const dim3 grid((unsigned)((N * kSubH + 255) / 256));
+    DC_HEADS_HB_EDGE(k_gat_softmax_heads_fwd, H, grid, stream, ptr, other, a_src, a_dst, slope, alpha, N, (int)H, a_edge);
+    return check_launch("dc_gat_edge_attr_softmax_fwd");
+}
+
+extern "C" int dc_gat_edge_attr_softmax_bwd(const int32_t *ptr, const int32_t *other, const float *a_src,
+                                            const float *a_dst, const float *a_edge, float slope, const float *alpha,
+                                            const float *galpha, float *ge, float *g_a_dst, int64_t N, int64_t H,
+                                            dc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DC_HEADS_SHAPE("dc_gat_edge_attr_softmax_bwd", N, H, 1);
+    if (N == 0) return DC_OK;
+    DC_REQUIRE(ptr && other && a_src && a_dst && a_edge && alpha && galpha && ge && g_a_dst,
+               "dc_gat_edge_attr_softmax_bwd: null pointer");
+    const dim3 grid((unsigned)((N * kSubH + 255) / 256));
+    DC_HEADS_HB_EDGE(k_gat_softmax_heads_bwd, H, grid, stream, ptr, other, a_src, a_dst, slope, alpha, galpha, ge,
+                     g_a_dst, N, (int)H, a_edge);
+    return check_launch("dc_gat_edge_attr_softmax_bwd");
 }
 
 extern "C" int dc_gat_edge_softmax_heads_bwd(const int32_t *ptr, const int32_t *other, const float *a_src,
@@ -495,7 +545,7 @@ extern "C" int dc_gat_edge_softmax_heads_bwd(const int32_t *ptr, const int32_t *
                "dc_gat_edge_softmax_heads_bwd: null pointer");
     const dim3 grid((unsigned)((N * kSubH + 255) / 256));
     DC_HEADS_HB(k_gat_softmax_heads_bwd, H, grid, stream, ptr, other, a_src, a_dst, slope, alpha, galpha, ge, g_a_dst, N,
-                (int)H);
+                (int)H, (const float *)nullptr);
     return check_launch("dc_gat_edge_softmax_heads_bwd");
 }
 

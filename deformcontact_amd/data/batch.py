@@ -83,7 +83,9 @@ class Batch(Data):
     """Block-diagonal union of graphs (``Batch.from_data_list``).
 
     Node-level tensors (first dim == ``num_nodes``) are concatenated on dim 0,
-    ``edge_index`` on dim 1 with the cumulative node offset added, other tensors
+    ``edge_index`` on dim 1 with the cumulative node offset added, ``edge_attr``
+    (first dim == ``num_edges``; decided by name, a graph can have E == N) on dim 0
+    in the order of ``edge_index``, other tensors
     are stacked on a new dim 0, non-tensors collected into lists.  ``batch [N]``
     maps nodes to graphs, ``ptr [B+1]`` are node offsets.  The concatenation
     order IS the edge order the sorted adjacency reproduces bit-exactly.
@@ -121,6 +123,10 @@ class Batch(Data):
             if k == "edge_index":
                 setattr(out, k, torch.cat([v + offs[i] for i, v in enumerate(vals)], dim=1))
                 kinds[k] = "edge"
+            elif k == "edge_attr" and all(isinstance(v, Tensor) and v.dim() >= 1 and v.size(0) == c
+                                          for v, c in zip(vals, ecounts)):
+                setattr(out, k, torch.cat(vals, dim=0))
+                kinds[k] = "edge_attr"
             elif isinstance(v0, Tensor) and v0.dim() >= 1 and all(
                     isinstance(v, Tensor) and v.size(0) == c for v, c in zip(vals, counts)):
                 setattr(out, k, torch.cat(vals, dim=0))
@@ -182,6 +188,8 @@ class Batch(Data):
             v = getattr(self, k)
             if kind == "edge":
                 d.edge_index = v[:, ea:ez] - a
+            elif kind == "edge_attr":
+                setattr(d, k, v[ea:ez])
             elif kind == "node":
                 setattr(d, k, v[a:z])
             else:

@@ -76,7 +76,8 @@ class GraphIndex:
     """CSR (by destination) + transposed (by source) views of one edge set."""
 
     def __init__(self, edge_index: Optional[torch.Tensor], num_nodes: int, *, self_loops: bool = False,
-                 normalize: bool = True, validate: bool = False, parts=None, segments=None):
+                 normalize: bool = True, validate: bool = False, parts=None, segments=None,
+                 loops_segmented: bool = False):
         #: ``(node offsets, edge offsets, B)`` host arrays when the one-launch segmented build applies
         self._segments = None
         #: merged (block-diagonal) adjacency: ``[(edge_index, num_nodes), ...]``; see ``from_parts``
@@ -152,6 +153,14 @@ class GraphIndex:
         if segments is not None and parts is None and not self_loops:
             self._segments = _segment_arrays(segments, self.num_nodes, self.num_input_edges, self.device)
             self._layout = _layout_arrays(segments, self.num_nodes)
+        elif segments is not None and parts is None and loops_segmented:
+            # OPT-IN, asked for by GATConv(edge_dim=...) alone - conv(x, knn_graph(pos, k, batch), edge_attr): the self-loop
+            # form dc_graph_build_segmented_loops.  Every other self-loop adjacency (GCNConv, GATConv without edge
+            # features) keeps the global pipeline and its launches.  Every workgroup of that build re-reads the input
+            # edges in front of its graph, graphs * E / 2 edges per side in all: taken up to SEG_LOOPS_MAX_WORK, beyond
+            # it the global pipeline runs.
+            if (len(segments[0]) - 1) * self.num_input_edges <= SEG_LOOPS_MAX_WORK:
+                self._segments = _segment_arrays(segments, self.num_nodes, self.num_input_edges, self.device)
         elif parts is not None and not self_loops:
             # merged node space: when every part's edge_index carries its batch layout (data.Batch._tag_edge_layout), the
             # merged space is a union of those graphs plus the isolated padding rows between the parts, which enter as graphs
@@ -196,9 +205,9 @@ class GraphIndex:
                current_stream_ptr(self.device))
         if self._segments is not None:
             nptr, eptr, nseg = self._segments
-            rc = _lib.lib().dc_graph_build_segmented(
-                self.edge_index.data_ptr(), self.num_input_edges, self.num_nodes, nptr, eptr, nseg,
-                *out[:9], out[11])
+            build = _lib.lib().dc_graph_build_segmented_loops if self.self_loops else _lib.lib().dc_graph_build_segmented
+            rc = build(self.edge_index.data_ptr(), self.num_input_edges, self.num_nodes, nptr, eptr, nseg,
+                       *out[:9], out[11])
             _lib.check(rc, "dc_graph_build_segmented")
         elif self.parts is not None:
             import ctypes
@@ -305,6 +314,10 @@ class GraphIndex:
 #: per-graph caps of the one-launch segmented build (include/deformcontact.h DC_SEG_MAX_NODES / DC_SEG_MAX_EDGES)
 SEG_MAX_NODES, SEG_MAX_EDGES = 4096, 16384
 SEGMENTED_BUILD = True
+#: graphs x input edges up to which the self-loop form of the segmented build is taken (GraphIndex.__init__).  Measured
+#: (profiles/r08/build_time.json): 24 vs 28 us of the global pipeline at 2 graphs x 12k edges, 32 vs 32 at 8 x 49k
+#: (graphs x E = 392k), 63 vs 55 at 32 x 196k, 201 vs 68 at 96 x 589k - its prefix count grows with graphs x E
+SEG_LOOPS_MAX_WORK = 1 << 19
 def _segment_arrays(segments, num_nodes: int, num_edges: int, device):
     """Validate the layout of a batch - ``segments = (node offsets, edge offsets)``, two ascending host sequences
     of B + 1 ints as ``Batch.from_data_list`` records them - and return it as the host arrays
@@ -429,7 +442,7 @@ def _key(edge_index, num_nodes, self_loops, normalize):
 
 
 def graph_index(edge_index: torch.Tensor, num_nodes: int, *, self_loops: bool = False,
-                normalize: bool = True, segments=None) -> GraphIndex:
+                normalize: bool = True, segments=None, loops_segmented: bool = False) -> GraphIndex:
     """The sorted adjacency of ``edge_index``, built on first use and cached on the tensor's
     address + version + shape.
 
@@ -442,7 +455,8 @@ def graph_index(edge_index: torch.Tensor, num_nodes: int, *, self_loops: bool = 
 
     ``segments`` = ``Batch.segments()`` of the batch this ``edge_index`` belongs to (host-side node / edge offsets
     of its graphs) selects the one-launch ``dc_graph_build_segmented`` when the layout qualifies; the arrays are the
-    same bit for bit.
+    same bit for bit.  ``loops_segmented``: a ``self_loops`` adjacency may take that build's self-loop form too (same
+    arrays up to ``ptr[N]``; an adjacency already cached for the key is returned whichever build made it).
     """
     key = _key(edge_index, num_nodes, self_loops, normalize)
     g = _cache_get(key, edge_index.device if edge_index.is_cuda else None)
@@ -450,7 +464,8 @@ def graph_index(edge_index: torch.Tensor, num_nodes: int, *, self_loops: bool = 
         return g
     if segments is None:
         segments = edge_layout(edge_index)       # the layout travels on the tensor (data.Batch._tag_edge_layout)
-    g = GraphIndex(edge_index, num_nodes, self_loops=self_loops, normalize=normalize, segments=segments)
+    g = GraphIndex(edge_index, num_nodes, self_loops=self_loops, normalize=normalize, segments=segments,
+                   loops_segmented=loops_segmented)
     _cache_put(key, g, (edge_index,))
     return g
 

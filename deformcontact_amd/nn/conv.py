@@ -9,7 +9,8 @@ unchanged:
 * ``TAGConv``: ``lins.{0..K}.weight [out,in]`` (no per-lin bias), ``bias [out]``;
 * ``GCNConv``: ``lin.weight [out,in]`` (glorot), ``bias [out]``;
 * ``GATConv``: ``lin.weight [H*out,in]`` (glorot), ``att_src/att_dst [1,H,out]``,
-  ``bias [H*out]`` (``concat=False``: ``[out]``).
+  ``bias [H*out]`` (``concat=False``: ``[out]``); with ``edge_dim=D`` also
+  ``lin_edge.weight [H*out,D]`` (glorot) and ``att_edge [1,H,out]``.
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -278,16 +279,27 @@ class GCNConv(nn.Module):
 
 class GATConv(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
-                 negative_slope: float = 0.2, bias: bool = True):
+                 negative_slope: float = 0.2, edge_dim: Optional[int] = None, fill_value="mean", bias: bool = True):
         super().__init__()
         if heads < 1:
             raise ValueError(f"heads must be >= 1, got {heads}")
+        if edge_dim is not None and not 1 <= edge_dim <= ops.GAT_EDGE_MAX_DIM:
+            raise ValueError(f"edge_dim must be within 1..{ops.GAT_EDGE_MAX_DIM} (the cap of the edge-feature kernels), "
+                             f"got {edge_dim}")
+        ops.gat_edge_fill(fill_value)                             # ("mean" or a Python float, else ValueError)
+        self.edge_dim, self.fill_value = edge_dim, fill_value
         self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, bool(concat)
         self.negative_slope = negative_slope
         self.lin = _Lin(in_channels, heads * out_channels, initializer="glorot")
         self.lin.six_products = True             # the attention vectors' gradient cancels to 1 % of its terms: 24-bit products
         self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
         self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
+        if edge_dim is not None:
+            self.lin_edge = _Lin(edge_dim, heads * out_channels, initializer="glorot")
+            self.att_edge = nn.Parameter(torch.empty(1, heads, out_channels))
+        else:
+            self.lin_edge = None
+            self.register_parameter("att_edge", None)
         if bias:
             self.bias = nn.Parameter(torch.zeros(self.out_width))
         else:
@@ -305,33 +317,74 @@ class GATConv(nn.Module):
         with torch.no_grad():
             self.att_src.uniform_(-a, a)
             self.att_dst.uniform_(-a, a)
+            if self.att_edge is not None:
+                self.att_edge.uniform_(-a, a)
             if self.bias is not None:
                 self.bias.zero_()
+        if self.lin_edge is not None:
+            self.lin_edge.reset_parameters()
 
     def graph_flags(self) -> dict:
         return dict(self_loops=True, normalize=False)
 
     def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
-        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
+        # a layer with edge features lets a tagged batch take the one-launch self-loop build; without edge_dim: as before
+        return graph_index(edge_index, num_nodes, segments=segments, loops_segmented=self.edge_dim is not None,
+                           **self.graph_flags())
 
     supports_fused_relu = True
 
-    def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
-        """``conv(x, edge_index)`` as PyG; everything behind ``lin`` is one autograd node on fused kernels
-        (``ops.gat_conv``, with several heads ``ops.gat_heads_conv``); ``relu=True`` also fuses the encoder's ReLU
-        (``models/model.py:71,77``)."""
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None, relu: bool = False,
+                next_conv=None) -> Tensor:
+        """``conv(x, edge_index)`` / ``conv(x, edge_index, edge_attr)`` as PyG; everything behind ``lin`` is one autograd
+        node on fused kernels (``ops.gat_conv``, with several heads ``ops.gat_heads_conv``, with edge features
+        ``ops.gat_heads_edge_conv``); ``relu=True`` also fuses the encoder's ReLU (``models/model.py:71,77``).
+        ``edge_attr``: float32 ``[E, edge_dim]`` (``[E]`` with ``edge_dim=1``) in the order of ``edge_index``, on the
+        device of ``x``; it enters the attention logits only.  A layer with ``edge_dim`` called without it has no edge
+        term."""
         x = resolve(x)
+        edge_attr = self._check_edge_attr(edge_attr, edge_index)
         _check_inputs(x, edge_index, self.in_channels)
+        if edge_attr is not None:
+            _require_cuda(edge_attr, "edge_attr")
+            if edge_attr.device != x.device:
+                raise RuntimeError(f"x is on {x.device} but edge_attr is on {edge_attr.device}")
         if DEFER_ACTIVATION and not relu and next_conv is None:
             side = _branch_stream(self, x)
-            return deferred(lambda act: _on_branch(side, lambda: self._layer(self.graph(edge_index, x.size(0)), x, act)),
-                            x.size(0), self.out_width, x, _grad_wanted(x, self)).guard(
-                                x, edge_index, *self.parameters())
+            wanted = _grad_wanted(x, self) or (edge_attr is not None and torch.is_grad_enabled()
+                                               and edge_attr.requires_grad)
+            return deferred(lambda act: _on_branch(side, lambda: self._layer(self.graph(edge_index, x.size(0)), x, act,
+                                                                             edge_attr)),
+                            x.size(0), self.out_width, x, wanted).guard(x, edge_index, edge_attr, *self.parameters())
         g = self.graph(edge_index, x.size(0))
-        return self._layer(g, x, relu)
+        return self._layer(g, x, relu, edge_attr)
 
-    def _layer(self, g: GraphIndex, x: Tensor, relu: bool) -> Tensor:
+    def _check_edge_attr(self, edge_attr, edge_index) -> Optional[Tensor]:
+        """The third positional argument as PyG's ``edge_attr`` ([E] -> [E, 1] with ``edge_dim=1``), checked on the host."""
+        if edge_attr is None:
+            return None
+        if not isinstance(edge_attr, Tensor):
+            raise TypeError(f"edge_attr (the third positional argument, as in PyG) must be a tensor, got "
+                            f"{type(edge_attr).__name__}; pass relu= / next_conv= by keyword")
+        edge_attr = resolve(edge_attr)
+        if self.edge_dim is None:
+            raise ValueError("edge_attr given to a GATConv built without edge_dim")
+        if edge_attr.dtype != torch.float32:
+            raise ValueError(f"edge_attr must be float32, got {edge_attr.dtype}")
+        if edge_attr.dim() == 1 and self.edge_dim == 1:
+            edge_attr = edge_attr.unsqueeze(-1)
+        if edge_attr.dim() != 2 or edge_attr.size(1) != self.edge_dim:
+            raise ValueError(f"edge_attr must be [E, {self.edge_dim}] (edge_dim = {self.edge_dim}), got "
+                             f"{tuple(edge_attr.shape)}")
+        if isinstance(edge_index, Tensor) and edge_index.dim() == 2 and edge_attr.size(0) != edge_index.size(1):
+            raise ValueError(f"edge_attr has {edge_attr.size(0)} rows but edge_index has {edge_index.size(1)} edges")
+        return edge_attr
+
+    def _layer(self, g: GraphIndex, x: Tensor, relu: bool, edge_attr: Optional[Tensor] = None) -> Tensor:
         h = self.lin(x)
+        if self.edge_dim is not None:
+            # a layer with edge features runs the multi-head kernels at every H >= 1, with or without edge_attr
+            return self._layer_heads(g, h, relu, edge_attr)
         if self.heads > 1:
             return self._layer_heads(g, h, relu)
         # one head (the mean over one head is that head: either value of ``concat``): the single-head kernels
@@ -344,22 +397,29 @@ class GATConv(nn.Module):
             out = out + self.bias
         return torch.relu(out) if relu else out
 
-    def _layer_heads(self, g: GraphIndex, h: Tensor, relu: bool) -> Tensor:
+    def _layer_heads(self, g: GraphIndex, h: Tensor, relu: bool, edge_attr: Optional[Tensor] = None) -> Tensor:
         """Several heads: the per-edge work on the kernels of dc_gat_heads.hip at every width; the row-wise passes fused
-        with it where ``ops.gat_heads_fused_ok``."""
+        with it where ``ops.gat_heads_fused_ok``.  ``edge_attr``: the edge term of dc_gat_edge.hip joins the logits, through
+        the folded ``M`` [edge_dim, H] (formed here, so autograd carries its gradient to ``lin_edge`` and ``att_edge``)."""
         nh, mean = self.heads, not self.concat
+        edge_m = ops.gat_edge_fold(self.lin_edge.weight, self.att_edge) if edge_attr is not None else None
         if ops.gat_heads_fused_ok(h, nh, mean):
+            if edge_attr is not None:
+                return ops.gat_heads_edge_conv(g, h, self.att_src, self.att_dst, self.bias, self.negative_slope, edge_attr,
+                                               edge_m, relu, nh, mean, self.fill_value)
             return ops.gat_heads_conv(g, h, self.att_src, self.att_dst, self.bias, self.negative_slope, relu, nh, mean)
         hv = h.view(-1, nh, self.out_channels)
         a_src = (hv * self.att_src).sum(-1)
         a_dst = (hv * self.att_dst).sum(-1)
-        out = ops.gat_heads_aggregate(g, h, a_src, a_dst, self.negative_slope, nh, mean)
+        out = ops.gat_heads_aggregate(g, h, a_src, a_dst, self.negative_slope, nh, mean, edge_attr, edge_m,
+                                      self.fill_value)
         if self.bias is not None:
             out = out + self.bias
         return torch.relu(out) if relu else out
 
     def extra_repr(self) -> str:
-        return f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
+        return (f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
+                + ("" if self.edge_dim is None else f", edge_dim={self.edge_dim}, fill_value={self.fill_value!r}"))
 
 
 # ``models/model.py:2`` imports ``knn`` from here (it never calls it): the device search of ``neighbors``

@@ -146,6 +146,18 @@ int dc_graph_build_segmented(const int64_t *edge_index, int64_t E, int64_t N,
                              int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
                              int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
                              int32_t *status, dc_stream_t stream);
+/* The self_loops = 1 form (the host layer takes it for small batches of GATConv(edge_dim) only), same arguments and caps; output arrays hold E + N entries.
+ * Input self loops are dropped and the loop of node i is appended with edge id E + i, last in its group; the edge count
+ * is ptr[N].  Still one launch per 96 graphs and no workspace: every workgroup counts the self loops among the input
+ * edges in front of its graph itself.  Writes the arrays dc_graph_build (self_loops = 1) writes up to ptr[N], bit for
+ * bit (gcn_norm degrees count the loop).  An edge that leaves its graph is flagged in status and kept as an edge of the
+ * graph's first node; a self loop outside its graph's node range is flagged and dropped.  The count costs a read of
+ * nseg * E / 2 edges per side: meant for small batches. */
+int dc_graph_build_segmented_loops(const int64_t *edge_index, int64_t E, int64_t N,
+                                   const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                                   int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
+                                   int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
+                                   int32_t *status, dc_stream_t stream);
 
 /* 30-bit Morton (Z-order) code of every point of pos [n, >=3] (fp32, leading dimension ld): each
  * axis is mapped from [lo[a], lo[a] + 1 / inv_extent[a]) to 10 bits (lo / inv_extent are HOST
@@ -683,6 +695,46 @@ int dc_gat_alpha_heads_bwd(const float *h, int64_t ldh, const float *ga_src, con
                            const float *att_src, const float *att_dst, float *gh, int64_t ldgh, int64_t N,
                            int64_t H, int64_t C, void *workspace, int64_t workspace_bytes, float *g_att_src,
                            float *g_att_dst, int accumulate, dc_stream_t stream);
+
+/* ---- GATConv edge features (edge_dim = D, edge_attr [E, D]) (dc_gat_edge.hip, dc_gat_heads.hip) ----
+ * PyG gat_conv.py with edge_attr: the logit of edge p into i from j and head k is
+ *   leaky_relu((a_src[j,k] + a_dst[i,k]) + a_edge[p,k]),  a_edge[p,k] = <lin_edge(edge_attr[p])[k,:], att_edge[k,:]>
+ * added in that order (an a_edge of zeros leaves every bit of the entries above).  The term is linear in edge_attr:
+ * a_edge[p,:] = attr[p,:] @ M with the caller's folded M [D, H] row-major, M[d,k] = sum_c lin_edge.weight[kC+c,d]
+ * att_edge[k,c]; [E, H*C] is never formed.  Arrays are in key_row=1 order of a self_loops=1 set (ptr / perm of
+ * dc_graph_build): sorted edge p is input edge perm[p] < E - row perm[p] of edge_attr, float32, row stride lda >= D,
+ * inner stride 1 - or the appended loop of node perm[p] - E, whose attribute row is fill_value: fill_mean != 0 the mean
+ * of the attribute rows of the other edges into the node, summed in p order from zero and divided by their count (0
+ * where there are none), else the constant fill_value in every component.  Input self loops were dropped by the build
+ * and appear nowhere.  1 <= D <= DC_GAT_EDGE_MAX_DIM, any H >= 1 and in-degree, E = 0 (edge_attr may be NULL), N = 1;
+ * sums in fixed order, no float atomics (deterministic).
+ *   dc_gat_edge_attr_fwd         : a_edge [capacity, H] edge-major (rows ptr[N].. untouched), sum over d in d order;
+ *                                  loop_attr [N, D] = the attribute row of every node's appended loop
+ *   dc_gat_edge_attr_softmax_fwd : dc_gat_edge_softmax_heads_fwd with the addend (same kernel template)
+ *   dc_gat_edge_attr_softmax_bwd : dc_gat_edge_softmax_heads_bwd with the addend: the leaky-relu derivative looks at
+ *                                  the full logit; ge is the gradient of the pre-activation logit, hence of a_edge
+ *   dc_gat_edge_attr_bwd         : g_edge_attr (NULL: skipped) [E, D], row stride ldg: row perm[p] =
+ *                                  (ge[p,:] + ge[loop of i,:] / cnt_i) @ M^T with fill_mean, ge[p,:] @ M^T without -
+ *                                  every input edge written by one thread, rows of dropped input self loops zero;
+ *                                  g_m (NULL: skipped) [D, H]: g_m[d,k] = sum_p attr[p,d] ge[p,k] over all sorted
+ *                                  edges p < ptr[N] (loops with loop_attr), per-workgroup partials of 1,024 edges in
+ *                                  the workspace (dc_gat_edge_attr_bwd_workspace_bytes(capacity, D, H)) combined in
+ *                                  workgroup order.  capacity = rows of ge (E + N). */
+#define DC_GAT_EDGE_MAX_DIM 64
+int dc_gat_edge_attr_fwd(const int32_t *ptr, const int32_t *perm, const float *edge_attr, int64_t lda, const float *m,
+                         int fill_mean, float fill_value, float *a_edge, float *loop_attr, int64_t N, int64_t E,
+                         int64_t D, int64_t H, dc_stream_t stream);
+int dc_gat_edge_attr_softmax_fwd(const int32_t *ptr, const int32_t *other, const float *a_src, const float *a_dst,
+                                 const float *a_edge, float slope, float *alpha, int64_t N, int64_t H,
+                                 dc_stream_t stream);
+int dc_gat_edge_attr_softmax_bwd(const int32_t *ptr, const int32_t *other, const float *a_src, const float *a_dst,
+                                 const float *a_edge, float slope, const float *alpha, const float *galpha, float *ge,
+                                 float *g_a_dst, int64_t N, int64_t H, dc_stream_t stream);
+int64_t dc_gat_edge_attr_bwd_workspace_bytes(int64_t capacity, int64_t D, int64_t H);
+int dc_gat_edge_attr_bwd(const int32_t *ptr, const int32_t *perm, const float *ge, const float *edge_attr, int64_t lda,
+                         const float *loop_attr, const float *m, int fill_mean, float *g_edge_attr, int64_t ldg,
+                         float *g_m, int64_t N, int64_t E, int64_t D, int64_t H, int64_t capacity, void *workspace,
+                         int64_t workspace_bytes, dc_stream_t stream);
 
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:

@@ -5,7 +5,10 @@
   (b) what the single-head kernels can do for the same layer: H ``heads=1`` layers over the weight slices + ``cat``,
   (c) the existing ``heads=1, C=256`` layer - same total width, same gathered bytes,
 
-forward and forward + backward, for (H, C) = (4, 64), (8, 32), (2, 128).  Prints one JSON line; ``--out`` also writes it.
+forward and forward + backward, for (H, C) = (4, 64), (8, 32), (2, 128).  ``--edge-dim D`` adds a leg per shape: the
+same (H, C) layer with ``edge_dim=D`` fed ``edge_attr`` [E, D] (gradient of ``edge_attr`` included) against the layer
+without edge features, with the byte model of the edge-term forward next to it (it reads E*D*4 B of attributes once
+and writes (E+N)*H*4 B; the softmax then reads those once more).  Prints one JSON line; ``--out`` also writes it.
 Needs a HIP device (no fallback).  Bytes model of (a)/(c) for the aggregation: both gather E' rows of 1 KiB and write N
 rows; (a) reads H weights per edge where (c) reads one - ``model_bytes_ratio`` below.
 """
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--edge-dim", type=int, default=0, help="also time the layers with edge features of this width")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("gat_heads_bench needs a HIP device")
@@ -57,6 +61,10 @@ def main():
     x = torch.from_numpy(rng.uniform(-1, 1, (N, FIN)).astype(np.float32)).to(dev).requires_grad_(True)
     gup = torch.from_numpy(rng.uniform(0.5, 1.5, (N, 256)).astype(np.float32)).to(dev)
     ep = E + N                                                    # edges with the self loops
+
+    ea = None
+    if args.edge_dim > 0:
+        ea = torch.from_numpy(rng.uniform(-1, 1, (E, args.edge_dim)).astype(np.float32)).to(dev).requires_grad_(True)
 
     def timed(layer_fn, params):
         def fwd():
@@ -76,13 +84,24 @@ def main():
     for nh, c in ((4, 64), (8, 32), (2, 128)):
         multi = dc.nn.GATConv(FIN, c, heads=nh).to(dev)
         singles = [dc.nn.GATConv(FIN, c).to(dev) for _ in range(nh)]
+        # aggregation traffic: gathered rows + written rows + adjacency (other, ptr) + weights per edge
+        rows = (ep + N) * 256 * 4 + ep * 4 + N * 4
         a_f, a_fb = timed(lambda: multi(x, ei, relu=True), list(multi.parameters()))
         b_f, b_fb = timed(lambda: torch.cat([s(x, ei, relu=True) for s in singles], 1),
                           [p for s in singles for p in s.parameters()])
-        # aggregation traffic: gathered rows + written rows + adjacency (other, ptr) + weights per edge
-        rows = (ep + N) * 256 * 4 + ep * 4 + N * 4
+        edge = {}
+        if ea is not None:
+            with_e = dc.nn.GATConv(FIN, c, heads=nh, edge_dim=args.edge_dim).to(dev)
+            e_f, e_fb = timed(lambda: with_e(x, ei, ea, relu=True), list(with_e.parameters()) + [ea])
+            # forward traffic of the layer behind lin without edge features (aggregation + softmax: the logits' operands,
+            # alpha written and read) and what the edge term adds (attributes read once, a_edge written, read by the softmax)
+            base = rows + ep * nh * 4 + 2 * ep * nh * 4 + 2 * N * nh * 4
+            extra = E * args.edge_dim * 4 + 2 * ep * nh * 4 + ep * 4
+            edge = {"edge_dim": args.edge_dim, "e_edge_features_ms": {"fwd": e_f, "fwd_bwd": e_fb},
+                    "e_over_a": {"fwd": e_f / a_f, "fwd_bwd": e_fb / a_fb},
+                    "model_bytes_ratio_fwd_e_over_a": (base + extra) / base}
         result["shapes"].append({
-            "H": nh, "C": c,
+            "H": nh, "C": c, **edge,
             "a_fused_heads_ms": {"fwd": a_f, "fwd_bwd": a_fb},
             "b_single_head_slices_ms": {"fwd": b_f, "fwd_bwd": b_fb},
             "a_over_b": {"fwd": a_f / b_f, "fwd_bwd": a_fb / b_fb},

@@ -170,7 +170,9 @@ class TAGConv(nn.Module):
         TAGConv that consumes this output) lets the output be written straight into that
         layer's hop slab; ``out_into`` (a ``[N, out]`` row-major view the caller owns, e.g. this
         branch's rows of a merged slab - ``ops.merged_slab_part``) receives the output instead."""
-        x = resolve(x)                 # (the deferred result of another plain conv call: its value, see deferred.py)
+        if self.K + 1 > ops.MAX_SEG:   # (here, not in the dense block: before the adjacency build and a deferred first use)
+            raise NotImplementedError(f"TAGConv K={self.K} > {ops.MAX_SEG - 1} is not supported by the fused dense block")
+        x = resolve(x)                # (the deferred result of another plain conv call: its value, see deferred.py)
         if x.dtype == torch.bfloat16:
             # bf16-STORED features (BASELINE.json configs[4]): bf16 hops with fp32 accumulation + the
             # bf16 MFMA dense block; forward only.  ``out_dtype`` of the last layer: self.bf16_out

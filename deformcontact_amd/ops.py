@@ -742,6 +742,12 @@ class _TagConvFn(torch.autograd.Function):
         six = next_geom is SIX_PRODUCTS
         if six:
             next_geom = None
+        ctx.empty = n == 0
+        if ctx.empty:
+            # no rows: nothing to launch (the kernels' entry points refuse the null pointers of empty tensors)
+            ctx.fi, ctx.has_bias = fi, bias is not None
+            ctx.save_for_backward(*weights)
+            return _tag_out_buffer(next_geom, n, fo, dev)
         concat, width, wpad = tag_slab_geometry(fi, k)
         path = _dense_path(fi, k, fo, six, concat and bool(L.dc_tag_linear_fwd_narrow_ok(fi, k + 1, wpad, fo)))
         need_x = ctx.needs_input_grad[1]
@@ -782,6 +788,12 @@ class _TagConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
+        if ctx.empty:                        # sums over no rows: an empty dX, zero dW and bias gradient
+            need = ctx.needs_input_grad
+            ws = ctx.saved_tensors
+            gx = gout.new_zeros((0, ctx.fi)) if need[1] else None
+            gb = gout.new_zeros(gout.size(1)) if (ctx.has_bias and need[2]) else None
+            return (None, gx, gb, None, None, *[torch.zeros_like(w) if need[5 + j] else None for j, w in enumerate(ws)])
         gout = _grad_layout(gout, 4)         # column-slice views (e.g. the dX slab) pass as is
         if ctx.path == "h2" and ctx.fo % 16 == 0:
             gx, gws, gb = _tag_backward_h2(ctx, gout)

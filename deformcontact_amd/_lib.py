@@ -179,6 +179,13 @@ _SIGNATURES = {
     "dc_gat_edge_attr_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "dc_gat_edge_attr_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, _vp, c_int, _vp, c_int64, _vp, c_int64, c_int64,
                                      c_int64, c_int64, c_int64, _vp, c_int64, _vp]),
+    "dc_gatv2_softmax_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_float, _vp, c_int64, c_int64, c_int64,
+                                     _vp]),
+    "dc_gatv2_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "dc_gatv2_softmax_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_float, _vp, _vp, c_int64, _vp,
+                                     c_int, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
+    "dc_gatv2_source_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_float, _vp,
+                                    c_int64, c_int64, c_int64, c_int64, _vp]),
 }
 
 

@@ -1,4 +1,4 @@
-"""``TAGConv`` / ``GCNConv`` / ``GATConv`` on the HIP hop kernels.
+"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` on the HIP hop kernels.
 
 Drop-in for the PyG classes the reference instantiates at
 ``/root/reference/models/model.py:39-50`` and calls at ``:71,77``.  Parameter
@@ -10,7 +10,9 @@ unchanged:
 * ``GCNConv``: ``lin.weight [out,in]`` (glorot), ``bias [out]``;
 * ``GATConv``: ``lin.weight [H*out,in]`` (glorot), ``att_src/att_dst [1,H,out]``,
   ``bias [H*out]`` (``concat=False``: ``[out]``); with ``edge_dim=D`` also
-  ``lin_edge.weight [H*out,D]`` (glorot) and ``att_edge [1,H,out]``.
+  ``lin_edge.weight [H*out,D]`` (glorot) and ``att_edge [1,H,out]``;
+* ``GATv2Conv``: ``lin_l.weight`` / ``lin_r.weight [H*out,in]`` (glorot) with ``lin_l.bias`` / ``lin_r.bias [H*out]``,
+  ``att [1,H,out]``, ``bias [H*out]`` (``concat=False``: ``[out]``); ``share_weights=True``: ``lin_r is lin_l``.
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -93,15 +95,20 @@ def _grad_wanted(x: Tensor, module: nn.Module) -> bool:
 
 
 class _Lin(nn.Module):
-    """Parameter holder mirroring ``torch_geometric.nn.dense.Linear(bias=False)``."""
+    """Parameter holder mirroring ``torch_geometric.nn.dense.Linear(bias=False)``; ``bias=True`` (GATv2Conv's linears):
+    with a bias ``[out]``, PyG's default ``U(+-1/sqrt(in))``."""
 
     #: set by GATConv on its ``lin``: keep the six-product dense kernels (``ops.dense_linear(six_products=True)``)
     six_products = False
 
-    def __init__(self, in_channels: int, out_channels: int, initializer: Optional[str] = None):
+    def __init__(self, in_channels: int, out_channels: int, initializer: Optional[str] = None, bias: bool = False):
         super().__init__()
         self.in_channels, self.out_channels, self.initializer = in_channels, out_channels, initializer
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -111,12 +118,16 @@ class _Lin(nn.Module):
             a = 1.0 / math.sqrt(self.in_channels)
         with torch.no_grad():
             self.weight.uniform_(-a, a)
+            if self.bias is not None:
+                b = 1.0 / math.sqrt(self.in_channels)
+                self.bias.uniform_(-b, b)
 
     def forward(self, x: Tensor) -> Tensor:
         x = resolve(x)
         if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32:
-            return ops.dense_linear(x, self.weight, six_products=self.six_products)      # the library's MFMA dense block
-        return torch.nn.functional.linear(x, self.weight)
+            # the library's MFMA dense block
+            return ops.dense_linear(x, self.weight, self.bias, six_products=self.six_products)
+        return torch.nn.functional.linear(x, self.weight, self.bias)
 
 
 def _check_inputs(x: Tensor, edge_index: Tensor, in_channels: int):
@@ -422,6 +433,84 @@ class GATConv(nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
                 + ("" if self.edge_dim is None else f", edge_dim={self.edge_dim}, fill_value={self.fill_value!r}"))
+
+
+class GATv2Conv(nn.Module):
+    """PyG 2.5.2 ``GATv2Conv`` (dynamic attention): ``e_ij = att . leaky_relu(lin_l(x_j) + lin_r(x_i))`` per head, edge
+    softmax over the incoming edges of i (self loops removed, then added), ``out_i = sum_j alpha_ij lin_l(x_j)``, the
+    heads side by side (``concat``) or averaged, ``+ bias``.  Not supported, and absent from the signature as for
+    ``GATConv``: attention dropout, ``add_self_loops=False``, ``edge_dim``, ``return_attention_weights``, bipartite
+    input, bf16-stored input."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
+                 negative_slope: float = 0.2, bias: bool = True, share_weights: bool = False):
+        super().__init__()
+        if heads < 1:
+            raise ValueError(f"heads must be >= 1, got {heads}")
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, bool(concat)
+        self.negative_slope, self.share_weights = negative_slope, bool(share_weights)
+        self.lin_l = _Lin(in_channels, heads * out_channels, initializer="glorot", bias=bias)
+        self.lin_r = self.lin_l if share_weights else _Lin(in_channels, heads * out_channels, initializer="glorot",
+                                                           bias=bias)
+        # as GATConv's ``lin``: the attention vector's gradient is a sum of terms that cancel - 24-bit products
+        self.lin_l.six_products = self.lin_r.six_products = True
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(self.out_width))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    @property
+    def out_width(self) -> int:
+        """Width of the output: the heads side by side (``concat``) or their mean."""
+        return self.heads * self.out_channels if self.concat else self.out_channels
+
+    def reset_parameters(self):
+        self.lin_l.reset_parameters()
+        if not self.share_weights:
+            self.lin_r.reset_parameters()
+        a = math.sqrt(6.0 / (self.heads + self.out_channels))
+        with torch.no_grad():
+            self.att.uniform_(-a, a)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def graph_flags(self) -> dict:
+        return dict(self_loops=True, normalize=False)
+
+    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
+        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
+
+    supports_fused_relu = True
+
+    def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
+        """``conv(x, edge_index)`` as PyG; everything behind the two linears is one autograd node on the kernels of
+        dc_gatv2.hip and dc_gat_heads.hip (``ops.gatv2_conv``); ``relu=True`` also fuses the ReLU that follows."""
+        x = resolve(x)
+        _check_inputs(x, edge_index, self.in_channels)
+        if DEFER_ACTIVATION and not relu and next_conv is None:
+            side = _branch_stream(self, x)
+            return deferred(lambda act: _on_branch(side, lambda: self._layer(self.graph(edge_index, x.size(0)), x, act)),
+                            x.size(0), self.out_width, x, _grad_wanted(x, self)).guard(x, edge_index, *self.parameters())
+        g = self.graph(edge_index, x.size(0))
+        return self._layer(g, x, relu)
+
+    def _layer(self, g: GraphIndex, x: Tensor, relu: bool) -> Tensor:
+        xl = self.lin_l(x)
+        xr = xl if self.share_weights else self.lin_r(x)
+        nh, mean = self.heads, not self.concat
+        if ops.gat_heads_fused_ok(xl, nh, mean):
+            return ops.gatv2_conv(g, xl, xr, self.att, self.bias, self.negative_slope, relu, nh, mean)
+        # widths the row-wise passes (mask, bias gradient) do not take: the per-edge kernels run all the same
+        out = ops.gatv2_conv(g, xl, xr, self.att, None, self.negative_slope, False, nh, mean)
+        if self.bias is not None:
+            out = out + self.bias
+        return torch.relu(out) if relu else out
+
+    def extra_repr(self) -> str:
+        return (f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
+                + (", share_weights=True" if self.share_weights else ""))
 
 
 # ``models/model.py:2`` imports ``knn`` from here (it never calls it): the device search of ``neighbors``

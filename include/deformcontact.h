@@ -736,6 +736,45 @@ int dc_gat_edge_attr_bwd(const int32_t *ptr, const int32_t *perm, const float *g
                          float *g_m, int64_t N, int64_t E, int64_t D, int64_t H, int64_t capacity, void *workspace,
                          int64_t workspace_bytes, dc_stream_t stream);
 
+/* ---- GATv2Conv: dynamic attention (dc_gatv2.hip) ----
+ * PyG gatv2_conv.py with xl = lin_l(x), xr = lin_r(x) viewed as [N, H, C] (row-major [N, H*C], row strides ld* >= H*C;
+ * xl == xr with share_weights).  For sorted edge p from j = other[p] into i, head k, channel c:
+ *   s[p,k,c] = xl[j,k,c] + xr[i,k,c],   e[p,k] = sum_c att[k,c] leaky_relu(s[p,k,c]),
+ *   alpha[p,k] = softmax of e[.,k] over segment i (maximum subtracted, denominator + 1e-16)
+ * att is the [1,H,C] parameter, flat.  alpha / galpha / ge are [capacity, H] edge-major in key_row=1 order, as for the
+ * entries of dc_gat_heads.hip, whose dc_spmm_f32_heads_bias_act (aggregation of xl) and dc_sddmm_f32_heads (galpha[p,k] =
+ * <gm[i,k,:], xl[j,k,:]>) the layer uses as they are.  Any H >= 1, C >= 1 and in-degree, N = 0; no width cap; 16-byte
+ * loads when C % 4 == 0 and every row is 16-byte aligned.  Sums in a fixed order (the long ones compensated), no float
+ * atomics: deterministic.  Arguments are checked before any HIP call, in this order in all three entries: sizes (N < 0,
+ * H < 1, C < 1, range), leading dimensions, then null pointers - DC_EINVAL with the entry's name in dc_last_error().
+ * N == 0 is the one exception to the null check: there is no row to read or write, so the per-row and per-edge arrays
+ * may be NULL (an empty tensor has no address) and the call returns DC_OK; dc_gatv2_softmax_bwd still needs att and
+ * g_att, which it writes (zeros, or g_att as it is with accumulate).
+ *   dc_gatv2_softmax_fwd : alpha (rows ptr[N].. untouched); one wave per destination, xr[i] in registers, every xl[j]
+ *                          element gathered once
+ *   dc_gatv2_softmax_bwd : ge[p,k] = alpha[p,k] (galpha[p,k] - sum over segment i of alpha galpha), the gradient of e;
+ *                          g_xr[i,k,c] = sum over the edges into i, in p order, of t[p,k,c] = ge[p,k] att[k,c]
+ *                          (s[p,k,c] > 0 ? 1 : slope); g_att[k,c] (+)= sum_p ge[p,k] leaky_relu(s[p,k,c]): one row of
+ *                          partial sums per workgroup of DC_GATV2_ROWS destinations in the workspace
+ *                          (dc_gatv2_workspace_bytes(N, H, C)), added in workgroup order; accumulate != 0 adds to what
+ *                          g_att holds
+ *   dc_gatv2_source_bwd  : on the key_row=0 set (ptr_t / other_t; to_fwd[q] = position of transposed edge q in key_row=1
+ *                          order): g_xl[j,k,c] = sum over the edges q out of j, in q order, of alpha[p,k] gm[i,k,c] +
+ *                          t[p,k,c] with p = to_fwd[q], i = other_t[q] - both terms in one walk of the segment */
+#define DC_GATV2_ROWS 32
+int dc_gatv2_softmax_fwd(const int32_t *ptr, const int32_t *other, const float *xl, int64_t ldxl, const float *xr,
+                         int64_t ldxr, const float *att, float slope, float *alpha, int64_t N, int64_t H, int64_t C,
+                         dc_stream_t stream);
+int64_t dc_gatv2_workspace_bytes(int64_t N, int64_t H, int64_t C);
+int dc_gatv2_softmax_bwd(const int32_t *ptr, const int32_t *other, const float *alpha, const float *galpha,
+                         const float *xl, int64_t ldxl, const float *xr, int64_t ldxr, const float *att, float slope,
+                         float *ge, float *g_xr, int64_t ldg, float *g_att, int accumulate, void *workspace,
+                         int64_t workspace_bytes, int64_t N, int64_t H, int64_t C, dc_stream_t stream);
+int dc_gatv2_source_bwd(const int32_t *ptr_t, const int32_t *other_t, const int32_t *to_fwd, const float *alpha,
+                        const float *ge, const float *gm, int64_t ldgm, const float *xl, int64_t ldxl, const float *xr,
+                        int64_t ldxr, const float *att, float slope, float *g_xl, int64_t ldg, int64_t N, int64_t H,
+                        int64_t C, dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

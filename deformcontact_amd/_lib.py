@@ -186,6 +186,11 @@ _SIGNATURES = {
                                      c_int, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
     "dc_gatv2_source_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_float, _vp,
                                     c_int64, c_int64, c_int64, c_int64, _vp]),
+    "dc_tconv_softmax_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, c_float, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_tconv_softmax_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, c_float, _vp, _vp, c_int64, c_int64, c_int64,
+                                     c_int64, _vp]),
+    "dc_tconv_source_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64,
+                                    c_int64, c_int64, c_int64, _vp]),
 }
 
 

@@ -1,4 +1,4 @@
-"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` on the HIP hop kernels.
+"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` on the HIP hop kernels.
 
 Drop-in for the PyG classes the reference instantiates at
 ``/root/reference/models/model.py:39-50`` and calls at ``:71,77``.  Parameter
@@ -12,7 +12,10 @@ unchanged:
   ``bias [H*out]`` (``concat=False``: ``[out]``); with ``edge_dim=D`` also
   ``lin_edge.weight [H*out,D]`` (glorot) and ``att_edge [1,H,out]``;
 * ``GATv2Conv``: ``lin_l.weight`` / ``lin_r.weight [H*out,in]`` (glorot) with ``lin_l.bias`` / ``lin_r.bias [H*out]``,
-  ``att [1,H,out]``, ``bias [H*out]`` (``concat=False``: ``[out]``); ``share_weights=True``: ``lin_r is lin_l``.
+  ``att [1,H,out]``, ``bias [H*out]`` (``concat=False``: ``[out]``); ``share_weights=True``: ``lin_r is lin_l``;
+* ``TransformerConv``: ``lin_key`` / ``lin_query`` / ``lin_value`` ``.weight [H*out,in]`` and ``.bias [H*out]``,
+  ``lin_skip.weight [W,in]`` (``W = H*out``, ``concat=False``: ``out``) with ``lin_skip.bias [W]`` when ``bias``, and
+  ``lin_beta.weight [1,3W]`` when ``beta`` - all ``U(+-1/sqrt(fan_in))``; no ``bias`` of the layer itself.
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -511,6 +514,90 @@ class GATv2Conv(nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
                 + (", share_weights=True" if self.share_weights else ""))
+
+
+class TransformerConv(nn.Module):
+    """PyG 2.5.2 ``TransformerConv`` (dot-product edge attention): ``e_ij = <lin_query(x_i), lin_key(x_j)> / sqrt(C)`` per
+    head, edge softmax over the incoming edges of i - the edge set exactly as given: no self loop is removed or added,
+    a node without in-edges aggregates 0 - ``out_i = sum_j alpha_ij lin_value(x_j)``, the heads side by side
+    (``concat``) or averaged; with ``root_weight`` ``+ lin_skip(x_i)``, with ``beta`` blended with it by the gate
+    ``sigmoid(lin_beta([out, r, out - r]))``.  ``bias`` governs ``lin_skip`` alone, which exists (and loads) also with
+    ``root_weight=False``, where it is not used.  Not supported, and absent from the signature: attention dropout,
+    ``edge_dim``, ``return_attention_weights``, bipartite input, bf16-stored input.  ``beta=True`` needs
+    ``root_weight`` (PyG silently ignores the gate without it; here it is a ``ValueError``)."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True, beta: bool = False,
+                 bias: bool = True, root_weight: bool = True):
+        super().__init__()
+        if heads < 1:
+            raise ValueError(f"heads must be >= 1, got {heads}")
+        if beta and not root_weight:
+            raise ValueError("beta=True gates the skip connection: it needs root_weight=True")
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, bool(concat)
+        self.beta, self.root_weight = bool(beta), bool(root_weight)
+        self.lin_key = _Lin(in_channels, heads * out_channels, bias=True)
+        self.lin_query = _Lin(in_channels, heads * out_channels, bias=True)
+        self.lin_value = _Lin(in_channels, heads * out_channels, bias=True)
+        self.lin_skip = _Lin(in_channels, self.out_width, bias=bias)
+        # the logit is a product of two linear outputs and feeds an exponential: 24-bit products in all of them
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip):
+            lin.six_products = True
+        self.lin_beta = _Lin(3 * self.out_width, 1) if beta else None
+
+    @property
+    def out_width(self) -> int:
+        """Width of the output: the heads side by side (``concat``) or their mean."""
+        return self.heads * self.out_channels if self.concat else self.out_channels
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip, self.lin_beta):
+            if lin is not None:
+                lin.reset_parameters()
+
+    def graph_flags(self) -> dict:
+        return dict(self_loops=False, normalize=False)
+
+    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
+        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
+
+    supports_fused_relu = True
+
+    def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
+        """``conv(x, edge_index)`` as PyG; the attention behind the three linears is one autograd node on the kernels of
+        dc_transformer.hip and dc_gat_heads.hip (``ops.transformer_conv``), the skip connection and the gate are torch
+        ops.  ``relu=True``: the ReLU that follows runs in the aggregation's epilogue with ``root_weight=False`` at
+        widths that pass ``ops.gat_heads_fused_ok``, else as a ``torch.relu`` behind the skip / gate."""
+        x = resolve(x)
+        _check_inputs(x, edge_index, self.in_channels)
+        if DEFER_ACTIVATION and not relu and next_conv is None:
+            side = _branch_stream(self, x)
+            return deferred(lambda act: _on_branch(side, lambda: self._layer(self._graph_of(edge_index, x), x, act)),
+                            x.size(0), self.out_width, x, _grad_wanted(x, self)).guard(x, edge_index, *self.parameters())
+        return self._layer(self._graph_of(edge_index, x), x, relu)
+
+    def _graph_of(self, edge_index: Tensor, x: Tensor) -> Optional[GraphIndex]:
+        # (no node: no adjacency to build, and ``ops.transformer_conv`` launches nothing)
+        return self.graph(edge_index, x.size(0)) if x.size(0) else None
+
+    def _layer(self, g: Optional[GraphIndex], x: Tensor, relu: bool) -> Tensor:
+        q, k, v = self.lin_query(x), self.lin_key(x), self.lin_value(x)
+        nh, mean = self.heads, not self.concat
+        if not self.root_weight:
+            fused = relu and ops.gat_heads_fused_ok(v, nh, mean)
+            out = ops.transformer_conv(g, q, k, v, None, fused, nh, mean)
+            return torch.relu(out) if relu and not fused else out
+        out = ops.transformer_conv(g, q, k, v, None, False, nh, mean)
+        r = self.lin_skip(x)
+        if self.lin_beta is not None:
+            b = torch.sigmoid(torch.nn.functional.linear(torch.cat([out, r, out - r], dim=-1), self.lin_beta.weight))
+            out = b * r + (1 - b) * out
+        else:
+            out = out + r
+        return torch.relu(out) if relu else out
+
+    def extra_repr(self) -> str:
+        return (f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
+                + (", beta=True" if self.beta else "") + ("" if self.root_weight else ", root_weight=False"))
 
 
 # ``models/model.py:2`` imports ``knn`` from here (it never calls it): the device search of ``neighbors``

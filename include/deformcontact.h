@@ -775,6 +775,37 @@ int dc_gatv2_source_bwd(const int32_t *ptr_t, const int32_t *other_t, const int3
                         int64_t ldxr, const float *att, float slope, float *g_xl, int64_t ldg, int64_t N, int64_t H,
                         int64_t C, dc_stream_t stream);
 
+/* ---- TransformerConv: scaled dot-product edge attention (dc_transformer.hip) ----
+ * PyG transformer_conv.py with q = lin_query(x), k = lin_key(x), v = lin_value(x) viewed as [N, H, C] (row-major
+ * [N, H*C], row strides ld* >= H*C).  For sorted edge p from j = other[p] into i and head h:
+ *   e[p,h] = (sum_c q[i,h,c] k[j,h,c]) * scale,   scale = float32(1 / sqrt(C)), given by the caller
+ *   alpha[p,h] = softmax of e[.,h] over segment i (maximum subtracted, denominator + 1e-16)
+ * alpha / galpha / gl are [capacity, H] edge-major in key_row=1 order, as for the entries of dc_gat_heads.hip, whose
+ * dc_spmm_f32_heads_bias_act (aggregation of v) and dc_sddmm_f32_heads (galpha[p,h] = <gm[i,h,:], v[j,h,:]>) the layer
+ * uses as they are.  The edge set is taken as given (no self loop is added): a row may have no edge.  Any H >= 1,
+ * C >= 1 and in-degree >= 0, N = 0; no width cap, no workspace; 16-byte loads when C % 4 == 0 and every row is 16-byte
+ * aligned.  Sums in a fixed order (the long ones compensated), no float atomics: deterministic.  Arguments are checked
+ * before any HIP call, in this order in all three entries: sizes (N < 0, H < 1, C < 1, range), leading dimensions,
+ * then null pointers - DC_EINVAL with the entry's name in dc_last_error().  N == 0 returns DC_OK before the null
+ * check (an empty tensor has no address).
+ *   dc_tconv_softmax_fwd : alpha (rows ptr[N].. untouched; nothing is written for a row without edges); one wave
+ *                          per destination, q[i] in registers, every k[j] element gathered once; a segment's exp /
+ *                          normalise passes are spread over the lanes of the head's group
+ *   dc_tconv_softmax_bwd : gl[p,h] = alpha[p,h] (galpha[p,h] - sum over segment i of alpha galpha) * scale, the gradient
+ *                          of <q_i, k_j>; g_q[i,h,c] = sum over the edges into i, in p order, of gl[p,h] k[j,h,c]
+ *                          (zeros for a row without edges); one launch
+ *   dc_tconv_source_bwd  : on the key_row=0 set (ptr_t / other_t; to_fwd[t] = position of transposed edge t in key_row=1
+ *                          order), with p = to_fwd[t], i = other_t[t], sums over the edges t out of j in t order:
+ *                          g_k[j,h,c] = sum gl[p,h] q[i,h,c] and g_v[j,h,c] = sum alpha[p,h] gm[i,h,c] - one walk */
+int dc_tconv_softmax_fwd(const int32_t *ptr, const int32_t *other, const float *q, int64_t ldq, const float *k,
+                         int64_t ldk, float scale, float *alpha, int64_t N, int64_t H, int64_t C, dc_stream_t stream);
+int dc_tconv_softmax_bwd(const int32_t *ptr, const int32_t *other, const float *alpha, const float *galpha,
+                         const float *k, int64_t ldk, float scale, float *gl, float *g_q, int64_t ldgq, int64_t N,
+                         int64_t H, int64_t C, dc_stream_t stream);
+int dc_tconv_source_bwd(const int32_t *ptr_t, const int32_t *other_t, const int32_t *to_fwd, const float *alpha,
+                        const float *gl, const float *q, int64_t ldq, const float *gm, int64_t ldgm, float *g_k,
+                        int64_t ldgk, float *g_v, int64_t ldgv, int64_t N, int64_t H, int64_t C, dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

@@ -191,6 +191,11 @@ _SIGNATURES = {
                                      c_int64, _vp]),
     "dc_tconv_source_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64,
                                     c_int64, c_int64, c_int64, _vp]),
+    "dc_sage_mean_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_sage_mean_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_sage_max_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_sage_max_bwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
+                                c_int64, _vp]),
 }
 
 

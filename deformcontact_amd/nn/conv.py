@@ -1,4 +1,4 @@
-"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` on the HIP hop kernels.
+"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` / ``SAGEConv`` on the HIP hop kernels.
 
 Drop-in for the PyG classes the reference instantiates at
 ``/root/reference/models/model.py:39-50`` and calls at ``:71,77``.  Parameter
@@ -15,7 +15,9 @@ unchanged:
   ``att [1,H,out]``, ``bias [H*out]`` (``concat=False``: ``[out]``); ``share_weights=True``: ``lin_r is lin_l``;
 * ``TransformerConv``: ``lin_key`` / ``lin_query`` / ``lin_value`` ``.weight [H*out,in]`` and ``.bias [H*out]``,
   ``lin_skip.weight [W,in]`` (``W = H*out``, ``concat=False``: ``out``) with ``lin_skip.bias [W]`` when ``bias``, and
-  ``lin_beta.weight [1,3W]`` when ``beta`` - all ``U(+-1/sqrt(fan_in))``; no ``bias`` of the layer itself.
+  ``lin_beta.weight [1,3W]`` when ``beta`` - all ``U(+-1/sqrt(fan_in))``; no ``bias`` of the layer itself;
+* ``SAGEConv``: ``lin_l.weight [out,in]`` with ``lin_l.bias [out]`` when ``bias``, ``lin_r.weight [out,in]`` when
+  ``root_weight``, ``lin.weight [in,in]`` and ``lin.bias [in]`` when ``project`` - all ``U(+-1/sqrt(fan_in))``.
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -598,6 +600,78 @@ class TransformerConv(nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
                 + (", beta=True" if self.beta else "") + ("" if self.root_weight else ", root_weight=False"))
+
+
+class SAGEConv(nn.Module):
+    """PyG 2.5.2 ``SAGEConv`` (GraphSAGE): ``out_i = lin_l(aggr_j x_j)`` over the incoming edges of i - the edge set
+    exactly as given: no self loop is removed or added, duplicates count, a node without in-edges aggregates 0 - with
+    ``root_weight`` ``+ lin_r(x_i)``, with ``normalize`` followed by ``F.normalize(out, p=2, dim=-1)``.  With ``project``
+    the SOURCE features are ``relu(lin(x))``; the root term keeps the raw ``x``.  ``bias`` governs ``lin_l`` alone
+    (``lin_r`` has none, ``lin`` always has one).  ``aggr``: ``"mean"``, ``"max"``, ``"sum"`` or its alias ``"add"``,
+    on ``ops.aggregate``; the max sends the gradient of every maximum in EQUAL shares to all edges that attain it
+    (INTEGRATION.md 1.5).  Not supported: any other ``aggr`` (lists and aggregation modules included; a
+    ``ValueError``), and - absent from the signature - bipartite ``(x_src, x_dst)`` input, ``size=``, bf16-stored
+    input."""
+
+    def __init__(self, in_channels: int, out_channels: int, aggr: str = "mean", normalize: bool = False,
+                 root_weight: bool = True, project: bool = False, bias: bool = True):
+        super().__init__()
+        if not isinstance(in_channels, int):
+            raise TypeError("SAGEConv: bipartite input (a pair of in_channels) is not supported")
+        if not isinstance(aggr, str) or aggr not in ("mean", "max", "sum", "add"):
+            raise ValueError(f"aggr must be 'mean', 'max', 'sum' or 'add', got {aggr!r}")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.aggr = "sum" if aggr == "add" else aggr
+        self.normalize, self.root_weight, self.project = bool(normalize), bool(root_weight), bool(project)
+        self.lin = _Lin(in_channels, in_channels, bias=True) if project else None
+        self.lin_l = _Lin(in_channels, out_channels, bias=bias)
+        self.lin_r = _Lin(in_channels, out_channels, bias=False) if root_weight else None
+
+    def reset_parameters(self):
+        for lin in (self.lin, self.lin_l, self.lin_r):
+            if lin is not None:
+                lin.reset_parameters()
+
+    def graph_flags(self) -> dict:
+        return dict(self_loops=False, normalize=False)
+
+    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
+        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
+
+    supports_fused_relu = True
+
+    def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
+        """``conv(x, edge_index)`` as PyG; the aggregation is one autograd node on the kernels of dc_sage.hip (the sum:
+        the unweighted hop), the linears run on the dense block.  ``relu=True``: the ReLU that follows runs in
+        ``lin_l``'s epilogue when nothing stands between them (``root_weight=False, normalize=False``), else as a
+        ``torch.relu`` behind the layer."""
+        x = resolve(x)
+        _check_inputs(x, edge_index, self.in_channels)
+        if DEFER_ACTIVATION and not relu and next_conv is None:
+            side = _branch_stream(self, x)
+            return deferred(lambda act: _on_branch(side, lambda: self._layer(self._graph_of(edge_index, x), x, act)),
+                            x.size(0), self.out_channels, x, _grad_wanted(x, self)).guard(x, edge_index, *self.parameters())
+        return self._layer(self._graph_of(edge_index, x), x, relu)
+
+    def _graph_of(self, edge_index: Tensor, x: Tensor) -> Optional[GraphIndex]:
+        # (no node: no adjacency to build, and ``ops.aggregate`` launches nothing)
+        return self.graph(edge_index, x.size(0)) if x.size(0) else None
+
+    def _layer(self, g: Optional[GraphIndex], x: Tensor, relu: bool) -> Tensor:
+        src = ops.dense_linear(x, self.lin.weight, self.lin.bias, relu=True) if self.lin is not None else x
+        agg = ops.aggregate(g, src, self.aggr)
+        if self.lin_r is None and not self.normalize:
+            return ops.dense_linear(agg, self.lin_l.weight, self.lin_l.bias, relu=relu)
+        out = self.lin_l(agg)
+        if self.lin_r is not None:
+            out = out + self.lin_r(x)
+        if self.normalize:
+            out = torch.nn.functional.normalize(out, p=2.0, dim=-1)
+        return torch.relu(out) if relu else out
+
+    def extra_repr(self) -> str:
+        return (f"{self.in_channels}, {self.out_channels}, aggr={self.aggr}" + (", normalize=True" if self.normalize else "")
+                + ("" if self.root_weight else ", root_weight=False") + (", project=True" if self.project else ""))
 
 
 # ``models/model.py:2`` imports ``knn`` from here (it never calls it): the device search of ``neighbors``

@@ -806,6 +806,34 @@ int dc_tconv_source_bwd(const int32_t *ptr_t, const int32_t *other_t, const int3
                         const float *gl, const float *q, int64_t ldq, const float *gm, int64_t ldgm, float *g_k,
                         int64_t ldgk, float *g_v, int64_t ldgv, int64_t N, int64_t H, int64_t C, dc_stream_t stream);
 
+/* ---- SAGEConv: mean and max over a node's in-edges (dc_sage.hip) ----
+ * Segment reductions of x fp32 [N, F] (row strides ld* >= F) over the key_row=1 set (ptr / other = source ids) as it
+ * is given - no self loop is added, duplicates count, a row may have no edge - and their backward over the key_row=0
+ * set (ptr_t / other_t = destination ids).  Any F >= 1 (no width cap), any in-degree >= 0, N = 0; 16-byte loads when
+ * F % 4 == 0 and every pointer and row stride is 16-byte aligned.  Sums in a fixed order (the backward sums
+ * compensated), no float atomics, no workspace: deterministic.  Inputs are finite; what a NaN does is unspecified.
+ * Arguments are checked before any HIP call, in this order: sizes (N < 0, F < 1, range), leading dimensions, then
+ * null pointers, then aliasing - DC_EINVAL with the entry's name in dc_last_error().  N == 0 returns DC_OK before the
+ * null check (an empty tensor has no address).
+ *   dc_sage_mean_fwd : y[i,c] = (sum over the edges p into i, in p order, of x[other[p],c]) / float(ptr[i+1] - ptr[i])
+ *                      - the plain fp32 sum of the unweighted dc_spmm_f32, then a true division; 0 for a row without
+ *                      edges
+ *   dc_sage_mean_bwd : gx[j,c] = sum over the edges t out of j, in t order, of gy[i,c] / float(in-degree of i),
+ *                      i = other_t[t], the in-degree read from the key_row=1 ptr; one launch, no scaled copy of gy
+ *   dc_sage_max_fwd  : m[i,c] = max over the edges into i of x[other[p],c]; cnt[i,c] (int32, NULL: not written) = the
+ *                      number of those edges whose value equals it; a row without edges gives m = 0, cnt = 0
+ *   dc_sage_max_bwd  : gx[j,c] = sum over the edges t out of j, in t order, of (x[j,c] == m[i,c]) gm[i,c] /
+ *                      float(cnt[i,c]): the gradient of m[i,c] split EVENLY among all edges that attain the maximum */
+int dc_sage_mean_fwd(const int32_t *ptr, const int32_t *other, const float *x, int64_t ldx, float *y, int64_t ldy,
+                     int64_t N, int64_t F, dc_stream_t stream);
+int dc_sage_mean_bwd(const int32_t *ptr_t, const int32_t *other_t, const int32_t *ptr, const float *gy, int64_t ldgy,
+                     float *gx, int64_t ldgx, int64_t N, int64_t F, dc_stream_t stream);
+int dc_sage_max_fwd(const int32_t *ptr, const int32_t *other, const float *x, int64_t ldx, float *m, int64_t ldm,
+                    int32_t *cnt, int64_t ldc, int64_t N, int64_t F, dc_stream_t stream);
+int dc_sage_max_bwd(const int32_t *ptr_t, const int32_t *other_t, const float *x, int64_t ldx, const float *m,
+                    int64_t ldm, const int32_t *cnt, int64_t ldc, const float *gm, int64_t ldgm, float *gx,
+                    int64_t ldgx, int64_t N, int64_t F, dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

@@ -196,6 +196,11 @@ _SIGNATURES = {
     "dc_sage_max_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
     "dc_sage_max_bwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
                                 c_int64, _vp]),
+    "dc_gine_fwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_gine_bwd_x": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, _vp, c_int64, _vp, c_int64, c_int64,
+                              c_int64, _vp]),
+    "dc_gine_bwd_e": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64,
+                              c_int64, _vp]),
 }
 
 

@@ -1,4 +1,5 @@
-"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` / ``SAGEConv`` on the HIP hop kernels.
+"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` / ``SAGEConv`` / ``GINConv`` / ``GINEConv`` on
+the HIP hop kernels.
 
 Drop-in for the PyG classes the reference instantiates at
 ``/root/reference/models/model.py:39-50`` and calls at ``:71,77``.  Parameter
@@ -17,7 +18,9 @@ unchanged:
   ``lin_skip.weight [W,in]`` (``W = H*out``, ``concat=False``: ``out``) with ``lin_skip.bias [W]`` when ``bias``, and
   ``lin_beta.weight [1,3W]`` when ``beta`` - all ``U(+-1/sqrt(fan_in))``; no ``bias`` of the layer itself;
 * ``SAGEConv``: ``lin_l.weight [out,in]`` with ``lin_l.bias [out]`` when ``bias``, ``lin_r.weight [out,in]`` when
-  ``root_weight``, ``lin.weight [in,in]`` and ``lin.bias [in]`` when ``project`` - all ``U(+-1/sqrt(fan_in))``.
+  ``root_weight``, ``lin.weight [in,in]`` and ``lin.bias [in]`` when ``project`` - all ``U(+-1/sqrt(fan_in))``;
+* ``GINConv`` / ``GINEConv``: ``eps [1]`` (a parameter with ``train_eps``, else a buffer), the keys of the user's module
+  under ``nn.``, and for ``GINEConv(edge_dim=D)`` ``lin.weight [in,D]`` and ``lin.bias [in]`` (``U(+-1/sqrt(D))``).
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -672,6 +675,142 @@ class SAGEConv(nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, aggr={self.aggr}" + (", normalize=True" if self.normalize else "")
                 + ("" if self.root_weight else ", root_weight=False") + (", project=True" if self.project else ""))
+
+
+def _reset_module(module: nn.Module) -> None:
+    """PyG's ``inits.reset``: a module's own ``reset_parameters`` if it has one, else that of its children."""
+    if hasattr(module, "reset_parameters"):
+        module.reset_parameters()
+    else:
+        for child in module.children():
+            _reset_module(child)
+
+
+class _GinBase(nn.Module):
+    """What ``GINConv`` and ``GINEConv`` share: the user's ``nn``, ``eps`` as a float32 ``[1]`` tensor named ``eps`` (a
+    Parameter with ``train_eps``, else a buffer), the edge set taken as it is given."""
+
+    def __init__(self, nn_: nn.Module, eps: float, train_eps: bool):
+        super().__init__()
+        self.nn = nn_
+        self.initial_eps = float(eps)
+        if train_eps:
+            self.eps = nn.Parameter(torch.empty(1))
+        else:
+            self.register_buffer("eps", torch.empty(1))
+        self.eps.data.fill_(self.initial_eps)
+
+    def reset_parameters(self):
+        _reset_module(self.nn)
+        self.eps.data.fill_(self.initial_eps)
+
+    def graph_flags(self) -> dict:
+        return dict(self_loops=False, normalize=False)
+
+    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
+        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}(nn={self.nn})"
+
+
+class GINConv(_GinBase):
+    """PyG 2.5.2 ``GINConv`` (graph isomorphism): ``out_i = nn((1 + eps) x_i + sum_j x_j)`` over the incoming edges
+    of i - the edge set exactly as given: no self loop is removed or added, duplicates count, a node without in-edges
+    gets ``(1 + eps) x_i``.  ``nn`` is any ``torch.nn.Module`` and is called as it is; the layer's result is ``nn``'s
+    result, so there is no ``relu=`` / ``next_conv=`` and no deferred result.  ``eps``: a ``[1]`` tensor in
+    ``state_dict`` either way, a Parameter with ``train_eps``.  The sum is the unweighted hop (``ops.aggregate(...,
+    "sum")``), the root term a torch op.  Not supported, and absent from the signature: bipartite ``(x_src, x_dst)``
+    input, ``size=``, bf16-stored input."""
+
+    def __init__(self, nn: nn.Module, eps: float = 0.0, train_eps: bool = False):
+        super().__init__(nn, eps, train_eps)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        """``conv(x, edge_index)`` as PyG; a deferred ``x`` is resolved."""
+        x = resolve(x)
+        _check_inputs(x, edge_index, x.size(1) if x.dim() == 2 else -1)
+        g = self.graph(edge_index, x.size(0)) if x.size(0) else None
+        return self.nn((1 + self.eps) * x + ops.aggregate(g, x, "sum"))
+
+
+class GINEConv(_GinBase):
+    """PyG 2.5.2 ``GINEConv`` (GIN with edge features): ``out_i = nn((1 + eps) x_i + sum_j relu(x_j + e_ji))`` over
+    the incoming edges of i - the edge set exactly as given: no self loop is removed or added, duplicates count, a node
+    without in-edges gets ``(1 + eps) x_i``.  With ``edge_dim`` ``e = lin(edge_attr)`` (``lin``: ``edge_dim ->
+    in_channels`` with a bias, on the dense block; ``in_channels`` inferred from ``nn`` as PyG does), without it
+    ``e = edge_attr``, whose width must then be ``x``'s.  The aggregation with the root term is one autograd node on
+    the kernels of dc_gine.hip (``ops.gine_aggregate``): the ReLU mask is recomputed in the backward, ``relu'(0) = 0``,
+    and ``eps`` is read on the device, so a trained ``eps`` may change between replays of a captured step
+    (INTEGRATION.md 1.6).  ``nn`` is any ``torch.nn.Module`` and is called as it is; the layer's result is ``nn``'s
+    result, so there is no ``relu=`` / ``next_conv=`` and no deferred result.  Not supported, and absent from the
+    signature: bipartite ``(x_src, x_dst)`` input, ``size=``, bf16-stored input."""
+
+    def __init__(self, nn: nn.Module, eps: float = 0.0, train_eps: bool = False, edge_dim: Optional[int] = None):
+        super().__init__(nn, eps, train_eps)
+        self.edge_dim = edge_dim
+        if edge_dim is not None:
+            first = nn[0] if isinstance(nn, torch.nn.Sequential) else nn
+            if hasattr(first, "in_features"):
+                in_channels = first.in_features
+            elif hasattr(first, "in_channels"):
+                in_channels = first.in_channels
+            else:
+                raise ValueError("Could not infer input channels from `nn`.")
+            self.lin = _Lin(edge_dim, in_channels, bias=True)
+        else:
+            self.lin = None
+
+    def reset_parameters(self):
+        super().reset_parameters()
+        if self.lin is not None:
+            self.lin.reset_parameters()
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None) -> Tensor:
+        """``conv(x, edge_index, edge_attr)`` as PyG.  ``edge_attr``: float32 ``[E, edge_dim]`` (``[E]`` where that
+        width is 1; without ``edge_dim`` ``[E, in_channels]``) with rows in the order of ``edge_index``, on the device
+        of ``x``; a column slice passes.  A deferred ``x`` or ``edge_attr`` is resolved."""
+        x = resolve(x)
+        edge_attr = self._check_edge_attr(edge_attr, edge_index, x)
+        _check_inputs(x, edge_index, self.lin.out_channels if self.lin is not None else (x.size(1) if x.dim() == 2
+                                                                                          else -1))
+        _require_cuda(edge_attr, "edge_attr")
+        if edge_attr.device != x.device:
+            raise RuntimeError(f"x is on {x.device} but edge_attr is on {edge_attr.device}")
+        g = self.graph(edge_index, x.size(0)) if x.size(0) else None
+        if self.lin is None:
+            e = edge_attr
+        elif edge_attr.size(0) == 0:
+            e = torch.nn.functional.linear(edge_attr, self.lin.weight, self.lin.bias)    # no edge: nothing to launch
+        else:
+            e = self.lin(edge_attr.contiguous())
+        return self.nn(ops.gine_aggregate(g, x, e, self.eps))
+
+    def _check_edge_attr(self, edge_attr, edge_index, x: Tensor) -> Tensor:
+        """The third positional argument as PyG's ``edge_attr`` ([E] -> [E, 1] where the width is 1), checked on the host."""
+        if edge_attr is None:
+            raise ValueError("GINEConv needs edge_attr: conv(x, edge_index, edge_attr)")
+        if not isinstance(edge_attr, Tensor):
+            raise TypeError(f"edge_attr (the third positional argument, as in PyG) must be a tensor, got "
+                            f"{type(edge_attr).__name__}")
+        edge_attr = resolve(edge_attr)
+        if edge_attr.dtype != torch.float32:
+            raise ValueError(f"edge_attr must be float32, got {edge_attr.dtype}")
+        width = self.edge_dim if self.edge_dim is not None else (x.size(1) if x.dim() == 2 else -1)
+        if edge_attr.dim() == 1 and width == 1:
+            edge_attr = edge_attr.unsqueeze(-1)
+        if edge_attr.dim() != 2:
+            raise ValueError(f"edge_attr must be [E, {width}], got {tuple(edge_attr.shape)}")
+        if edge_attr.size(1) != width:
+            if self.edge_dim is None:
+                raise ValueError("Node and edge feature dimensionalities do not match. Consider setting the 'edge_dim' "
+                                 f"attribute of 'GINEConv' (x has {x.size(1)} columns, edge_attr {edge_attr.size(1)})")
+            raise ValueError(f"edge_attr must be [E, {width}] (edge_dim = {width}), got {tuple(edge_attr.shape)}")
+        if isinstance(edge_index, Tensor) and edge_index.dim() == 2 and edge_attr.size(0) != edge_index.size(1):
+            raise ValueError(f"edge_attr has {edge_attr.size(0)} rows but edge_index has {edge_index.size(1)} edges")
+        if edge_attr.size(0) > 0 and edge_attr.size(1) > 1 and edge_attr.stride(1) != 1:
+            raise ValueError("edge_attr: innermost dimension must be contiguous")
+        return edge_attr
 
 
 # ``models/model.py:2`` imports ``knn`` from here (it never calls it): the device search of ``neighbors``

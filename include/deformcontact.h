@@ -834,6 +834,35 @@ int dc_sage_max_bwd(const int32_t *ptr_t, const int32_t *other_t, const float *x
                     int64_t ldm, const int32_t *cnt, int64_t ldc, const float *gm, int64_t ldgm, float *gx,
                     int64_t ldgx, int64_t N, int64_t F, dc_stream_t stream);
 
+/* ---- GINEConv: sum over a node's in-edges of relu(x_j + e_ji), the root term, and the backward (dc_gine.hip) ----
+ * x fp32 [N, F] are the node rows, e fp32 [E, F] the edge rows in the order of the INPUT edges (row strides ld* >= F);
+ * the key_row=1 set (ptr / other = source ids / perm = input edge id of every sorted position) and the key_row=0 set
+ * (ptr_t / other_t = destination ids / perm_t) are those of an edge set taken as it is given - no self loop is added,
+ * duplicates count, a row may have no edge - so perm is a bijection over the input edges.  eps: DEVICE pointer to one
+ * float, read by the kernel (it may change between two replays of a captured launch); NULL: no root term.  Any F >= 1
+ * (no width cap), any in-degree >= 0; 16-byte loads when F % 4 == 0 and every pointer and row stride is 16-byte
+ * aligned.  Sums in a fixed order, no float atomics, no workspace, no host read: deterministic and capturable.  The
+ * ReLU mask of the backward is recomputed from the same fp32 add as the forward (the same bits); relu'(0) = 0.
+ * Arguments are checked before any HIP call, in the order of the SAGE entries: sizes, leading dimensions, then null
+ * pointers, then aliasing.  N == 0 (dc_gine_bwd_e: E == 0) returns DC_OK before the null check.
+ *   dc_gine_fwd   : s = 0; for p in [ptr[i], ptr[i+1]) in order s += max(x[other[p],c] + e[perm[p],c], 0);
+ *                   y[i,c] = (1 + eps) * x[i,c] + s - 1 + eps formed first in fp32, then the product, then the add; plain
+ *                   fp32 sums, no contraction.  e is never read for a set without edges.
+ *   dc_gine_bwd_x : gx[j,c] = (1 + eps) * gy[j,c] + sum over the edges t out of j, in t order, of
+ *                   (x[j,c] + e[perm_t[t],c] > 0) * gy[other_t[t],c]; the sum compensated
+ *   dc_gine_bwd_e : ge[q,c] = (x[src[q],c] + e[q,c] > 0) * gy[dst[q],c] for every input edge q < E - src / dst: the two
+ *                   rows of the int64 edge list the sets were built from; every row of ge is written exactly once; an
+ *                   edge with an endpoint outside [0, N) gets a zero row */
+int dc_gine_fwd(const int32_t *ptr, const int32_t *other, const int32_t *perm, const float *x, int64_t ldx,
+                const float *e, int64_t lde, const float *eps, float *y, int64_t ldy, int64_t N, int64_t F,
+                dc_stream_t stream);
+int dc_gine_bwd_x(const int32_t *ptr_t, const int32_t *other_t, const int32_t *perm_t, const float *x, int64_t ldx,
+                  const float *e, int64_t lde, const float *eps, const float *gy, int64_t ldgy, float *gx, int64_t ldgx,
+                  int64_t N, int64_t F, dc_stream_t stream);
+int dc_gine_bwd_e(const int64_t *src, const int64_t *dst, const float *x, int64_t ldx, const float *e, int64_t lde,
+                  const float *gy, int64_t ldgy, float *ge, int64_t ldge, int64_t N, int64_t E, int64_t F,
+                  dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

@@ -5,34 +5,15 @@
 // the incoming edges of i, utils/_softmax.py) and the backward of that chain.
 // All arrays are in destination-sorted order (dc_csr_build key_row=1,
 // self_loops=1); the aggregation itself is dc_spmm_f32 with w = alpha.
-#include "dc_common.h"
+#include "dc_segment.h"
 
 namespace dc {
-
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
 
 // kSub lanes per destination segment (mean in-degree of the reference's meshes + the self loop is
 // 7): lane `sub` of a group walks edges beg + sub, beg + sub + kSub, ...  Segments are contiguous in
 // p, so the alpha / galpha / ge accesses of a wave are coalesced; max / sum / dot are reduced
 // inside the group with xor shuffles.  Group reductions of floats are order-fixed (deterministic).
 constexpr int kSub = 8;
-
-__device__ __forceinline__ float sub_max(float v) {
-#pragma unroll
-    for (int d = kSub / 2; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, kWave));
-    return v;
-}
-__device__ __forceinline__ float sub_sum(float v) {
-#pragma unroll
-    for (int d = kSub / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
 
 __global__ void __launch_bounds__(256)
 k_gat_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
@@ -45,14 +26,14 @@ k_gat_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ o
     const float ad = live ? a_dst[i] : 0.f;
     float m = -INFINITY;
     for (int p = beg + sub; p < end; p += kSub) m = fmaxf(m, lrelu(a_src[other[p]] + ad, slope));
-    m = sub_max(m);
+    m = sub_max<kSub>(m);
     float s = 0.f;
     for (int p = beg + sub; p < end; p += kSub) {
         const float ex = expf(lrelu(a_src[other[p]] + ad, slope) - m);
         alpha[p] = ex;
         s += ex;
     }
-    const float denom = sub_sum(s) + 1e-16f;
+    const float denom = sub_sum<kSub>(s) + 1e-16f;
     for (int p = beg + sub; p < end; p += kSub) alpha[p] = alpha[p] / denom;   // own elements only
 }
 
@@ -68,7 +49,7 @@ k_gat_softmax_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ o
     const float ad = live ? a_dst[i] : 0.f;
     float dot = 0.f;
     for (int p = beg + sub; p < end; p += kSub) dot += alpha[p] * galpha[p];
-    dot = sub_sum(dot);
+    dot = sub_sum<kSub>(dot);
     float acc = 0.f;
     for (int p = beg + sub; p < end; p += kSub) {
         const float s = a_src[other[p]] + ad;
@@ -76,7 +57,7 @@ k_gat_softmax_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ o
         ge[p] = g;
         acc += g;
     }
-    acc = sub_sum(acc);
+    acc = sub_sum<kSub>(acc);
     if (live && sub == 0) g_a_dst[i] = acc;
 }
 
@@ -181,7 +162,7 @@ extern "C" int dc_sddmm_f32(const int32_t *ptr, const int32_t *other, const floa
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && g && h && d, "dc_sddmm_f32: null pointer");
     DC_REQUIRE(ldg >= F && ldh >= F, "dc_sddmm_f32: leading dimension smaller than F");
-    const bool vec4 = F % 4 == 0 && ldg % 4 == 0 && ldh % 4 == 0 && (((uintptr_t)g | (uintptr_t)h) & 15) == 0;
+    const bool vec4 = F % 4 == 0 && ldg % 4 == 0 && ldh % 4 == 0 && al16(g) && al16(h);
     if (vec4)
         DC_LAUNCH((k_sddmm<4>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                            ptr, other, g, ldg, h, ldh, d, N, (int)F);

@@ -5,30 +5,19 @@
 // M[d, k] = sum_c lin_edge.weight[k C + c, d] att_edge[k, c] ([D, H] row-major, formed by the caller): [E, H*C] never
 // exists.  The appended self loop of node i (edge id E + i) carries fill_value: the mean of the attribute rows of the other
 // edges into i, or a constant.  The softmax with the extra addend shares the kernel templates of dc_gat_heads.hip and
-// lives there (dc_gat_edge_attr_softmax_fwd / _bwd).  Rules as stated at the top of dc_gat_heads.hip: destination-sorted
-// segments, sums in p order (the mean) and in d / k order (the products with M), products and sums rounded separately,
+// lives there (dc_gat_edge_attr_softmax_fwd / _bwd).  Rules of the segment kernels (helpers: see dc_segment.h):
+// destination-sorted segments, sums in p order (the mean) and in d / k order (the products with M), products and sums rounded separately,
 // no float atomics - two runs give the same bits.
-#include "dc_common.h"
+#include "dc_segment.h"
 
 #pragma clang fp contract(off)
 
 namespace dc {
 
-constexpr int kSubE = 8;                      // lanes per destination segment (kSubH of dc_gat_heads.hip)
+constexpr int kSubE = 8;                      // lanes per destination segment, as kSubH of dc_gat_heads.hip
 constexpr int kSegsE = 256 / kSubE;           // segments per workgroup
 constexpr int kMaxD = DC_GAT_EDGE_MAX_DIM;    // the loop attributes of a workgroup's segments sit in LDS: 32 x 64 floats
 constexpr int kGmChunk = 1024;                // sorted edges per workgroup of the gM partial pass
-
-__device__ __forceinline__ int sube_max(int v) {
-#pragma unroll
-    for (int d = kSubE / 2; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, kWave));
-    return v;
-}
-__device__ __forceinline__ int sube_sum(int v) {
-#pragma unroll
-    for (int d = kSubE / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
 
 // One group of kSubE lanes per destination segment.  Pass 1, lane = attribute column: the loop attribute of the node, the
 // running sum over the segment's input edges in p order divided by their count (or the constant).  Pass 2, lane = edge:
@@ -101,8 +90,8 @@ k_gat_edge_term_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
         if (perm[p] >= E) pl = p;
         else ++cnt;
     }
-    pl = sube_max(pl);
-    cnt = sube_sum(cnt);
+    pl = sub_max<kSubE>(pl);
+    cnt = sub_sum<kSubE>(cnt);
     const bool through_mean = fill_mean && pl >= 0 && cnt > 0;
     for (int k0 = 0; k0 < H; k0 += HB) {
         float gl[HB];

@@ -7,41 +7,17 @@
 // read of other[p] and one of the segment bounds serve every head and every neighbour row of H*C floats is gathered
 // once.  Same rules as the single-head kernels: destination-sorted segments, sums in p order, products and sums rounded
 // separately, no float atomics - two runs give the same bits.
-#include "dc_common.h"
+#include "dc_segment.h"
 
 #pragma clang fp contract(off)
 
 namespace dc {
-
-__device__ __forceinline__ float lrelu_h(float v, float slope) { return v > 0.f ? v : slope * v; }
-
-__device__ __forceinline__ float wave_sum_h(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-// sum over aligned groups of T lanes (T a power of two <= 64), fixed butterfly
-__device__ __forceinline__ float group_sum_h(float v, int T) {
-    for (int d = T >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
 
 // kSubH lanes per destination segment, as k_gat_softmax_fwd (dc_gat.hip): lane `sub` walks edges beg + sub,
 // beg + sub + kSubH, ... and carries HB heads of each edge in registers - one walk of the segment (one read of
 // other[p]) per pass serves HB heads; H > HB repeats the walk per block of heads.  Per head the arithmetic is that of
 // the single-head kernel, in the same order.
 constexpr int kSubH = 8;
-
-__device__ __forceinline__ float subh_max(float v) {
-#pragma unroll
-    for (int d = kSubH / 2; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, kWave));
-    return v;
-}
-__device__ __forceinline__ float subh_sum(float v) {
-#pragma unroll
-    for (int d = kSubH / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
 
 // EDGE (GATConv(edge_dim=...), dc_gat_edge.hip): the logit carries a third, per-edge addend a_edge[p, k] - added to the
 // finished a_src + a_dst, so an a_edge of zeros leaves every bit as it is; EDGE = false is the code without the operand.
@@ -74,10 +50,10 @@ k_gat_softmax_heads_fwd(const int32_t *__restrict__ ptr, const int32_t *__restri
             const float *ae = EDGE ? a_edge + (int64_t)p * H + k0 : nullptr;
 #pragma unroll
             for (int b = 0; b < HB; ++b)
-                if (k0 + b < H) m[b] = fmaxf(m[b], lrelu_h(logit_h<EDGE>(as[b], ad[b], ae, b), slope));
+                if (k0 + b < H) m[b] = fmaxf(m[b], lrelu(logit_h<EDGE>(as[b], ad[b], ae, b), slope));
         }
 #pragma unroll
-        for (int b = 0; b < HB; ++b) m[b] = subh_max(m[b]);
+        for (int b = 0; b < HB; ++b) m[b] = sub_max<kSubH>(m[b]);
         for (int p = beg + sub; p < end; p += kSubH) {
             const float *as = a_src + (int64_t)other[p] * H + k0;
             const float *ae = EDGE ? a_edge + (int64_t)p * H + k0 : nullptr;
@@ -85,13 +61,13 @@ k_gat_softmax_heads_fwd(const int32_t *__restrict__ ptr, const int32_t *__restri
 #pragma unroll
             for (int b = 0; b < HB; ++b)
                 if (k0 + b < H) {
-                    const float ex = expf(lrelu_h(logit_h<EDGE>(as[b], ad[b], ae, b), slope) - m[b]);
+                    const float ex = expf(lrelu(logit_h<EDGE>(as[b], ad[b], ae, b), slope) - m[b]);
                     al[b] = ex;
                     s[b] += ex;
                 }
         }
 #pragma unroll
-        for (int b = 0; b < HB; ++b) s[b] = subh_sum(s[b]) + 1e-16f;
+        for (int b = 0; b < HB; ++b) s[b] = sub_sum<kSubH>(s[b]) + 1e-16f;
         for (int p = beg + sub; p < end; p += kSubH) {          // own elements only
             float *al = alpha + (int64_t)p * H + k0;
 #pragma unroll
@@ -127,7 +103,7 @@ k_gat_softmax_heads_bwd(const int32_t *__restrict__ ptr, const int32_t *__restri
                 if (k0 + b < H) dot[b] += al[b] * ga[b];
         }
 #pragma unroll
-        for (int b = 0; b < HB; ++b) dot[b] = subh_sum(dot[b]);
+        for (int b = 0; b < HB; ++b) dot[b] = sub_sum<kSubH>(dot[b]);
         for (int p = beg + sub; p < end; p += kSubH) {
             const float *as = a_src + (int64_t)other[p] * H + k0;
             const float *al = alpha + (int64_t)p * H + k0, *ga = galpha + (int64_t)p * H + k0;
@@ -144,19 +120,13 @@ k_gat_softmax_heads_bwd(const int32_t *__restrict__ ptr, const int32_t *__restri
         }
 #pragma unroll
         for (int b = 0; b < HB; ++b) {
-            acc[b] = subh_sum(acc[b]);
+            acc[b] = sub_sum<kSubH>(acc[b]);
             if (live && sub == 0 && k0 + b < H) g_a_dst[i * H + k0 + b] = acc[b];
         }
     }
 }
 
 // ---- the aggregation: one wave per destination row, as k_spmm_wave (dc_spmm.hip) --------------------------------------
-template <int VEC> struct VecH;
-template <> struct VecH<1> { using T = float; };
-template <> struct VecH<4> { using T = float4; };
-
-__device__ __forceinline__ float hzero(float) { return 0.0f; }
-__device__ __forceinline__ float4 hzero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ void haxpy(float &acc, float w, float v) {
     const float m = w * v;
     acc = acc + m;
@@ -182,7 +152,7 @@ __global__ void __launch_bounds__(256)
 k_spmm_heads(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other, const float *__restrict__ alpha,
              const float *__restrict__ x, int64_t ldx, const float *__restrict__ bias, int relu, float *y,
              int64_t ldy, int64_t N, int H, int C) {
-    using V = typename VecH<VEC>::T;
+    using V = typename Vec<VEC>::T;
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
     const int64_t row = __builtin_amdgcn_readfirstlane((int)(lb * 4u + (threadIdx.x >> 6)));
     if (row >= N) return;
@@ -190,11 +160,11 @@ k_spmm_heads(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
     const int beg = ptr[row], end = ptr[row + 1];
     const int fout = MEAN ? C : H * C;
     for (int c = lane * VEC; c < fout; c += kWave * VEC) {
-        V tot = hzero(V{});
+        V tot = vec_zero(V{});
         const int k0 = MEAN ? 0 : c / C, k1 = MEAN ? H : k0 + 1;
         for (int k = k0; k < k1; ++k) {
             const int col = MEAN ? k * C + c : c;
-            V acc = hzero(V{});
+            V acc = vec_zero(V{});
             for (int p = beg; p < end; p += U) {
                 const int n = end - p;   // wave-uniform
                 int s[U];
@@ -246,7 +216,7 @@ __device__ __forceinline__ void sddmm_chunk(const float4 gv, int c0, int F, int 
 #pragma unroll
     for (int u = 0; u < U; ++u)
         if (u < n) {                                           // wave-uniform
-            const float t = group_sum_h(acc[u], T);
+            const float t = group_sum(acc[u], T);
             if (c0 < F && (lane & (T - 1)) == 0) d[(int64_t)(p + u) * H + c0 / C] = t;
         }
 }
@@ -297,7 +267,7 @@ k_sddmm_heads_any(const int32_t *__restrict__ ptr, const int32_t *__restrict__ o
         for (int k = 0; k < H; ++k) {
             float acc = 0.f;
             for (int c = lane; c < C; c += kWave) acc += g[row * ldg + k * C + c] * h[s * ldh + k * C + c];
-            acc = wave_sum_h(acc);
+            acc = wave_sum(acc);
             if (lane == 0) d[(int64_t)p * H + k] = acc;
         }
     }
@@ -353,8 +323,8 @@ k_gat_alpha_heads_fwd_v4(const float *__restrict__ h, int64_t ldh, const float *
             s = v.x * as.x + v.y * as.y + v.z * as.z + v.w * as.w;
             d = v.x * ad.x + v.y * ad.y + v.z * ad.z + v.w * ad.w;
         }
-        s = group_sum_h(s, T);
-        d = group_sum_h(d, T);
+        s = group_sum(s, T);
+        d = group_sum(d, T);
         if (c < F && (lane & (T - 1)) == 0) a_src[row * H + c / C] = s, a_dst[row * H + c / C] = d;
     }
 }
@@ -372,8 +342,8 @@ k_gat_alpha_heads_fwd_any(const float *__restrict__ h, int64_t ldh, const float 
             s += v * att_src[c];
             d += v * att_dst[c];
         }
-        s = wave_sum_h(s);
-        d = wave_sum_h(d);
+        s = wave_sum(s);
+        d = wave_sum(d);
         if (lane == 0) a_src[row * H + k] = s, a_dst[row * H + k] = d;
     }
 }
@@ -442,14 +412,9 @@ k_colsum_final_heads(const float *__restrict__ partial, int64_t nblocks, int64_t
     if (lane == 0) out[c] = accumulate ? out[c] + s : s;
 }
 
-static inline bool h_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 static inline bool h_pow2(int64_t v) { return v >= 1 && (v & (v - 1)) == 0; }
 // C % 4 == 0 and a head = an aligned group of C / 4 <= 64 lanes
 static inline bool h_group_ok(int64_t C) { return C % 4 == 0 && h_pow2(C / 4) && C / 4 <= kWave; }
-static inline bool h_width_ok(int64_t F) { return F >= 4 && F <= 1024 && F % 4 == 0 && 256 % (F / 4) == 0; }
-static inline bool h_sizes_ok(int64_t N, int64_t H, int64_t C) {
-    return N < (int64_t)INT32_MAX / 4 && H < (1 << 16) && C < (1 << 24) && H * C < (1 << 24);
-}
 
 }  // namespace dc
 
@@ -458,7 +423,7 @@ using namespace dc;
 #define DC_HEADS_SHAPE(name, N, H, C)                                                                              \
     DC_REQUIRE((N) >= 0 && (H) >= 1 && (C) >= 1, name ": need N >= 0, H >= 1, C >= 1 (N=%lld H=%lld C=%lld)",     \
                (long long)(N), (long long)(H), (long long)(C));                                                    \
-    DC_REQUIRE(h_sizes_ok(N, H, C), name ": size out of range")
+    DC_REQUIRE(sizes_ok(N, H, C), name ": size out of range")
 
 #define DC_HEADS_HB(kernel, H, grid, stream, ...)                                                       \
     do {                                                                                                 \
@@ -483,7 +448,7 @@ extern "C" int dc_gat_alpha_heads_fwd(const float *h, int64_t ldh, const float *
     DC_REQUIRE(ldh >= H * C, "dc_gat_alpha_heads_fwd: leading dimension smaller than H * C");
     if (N == 0) return DC_OK;
     DC_REQUIRE(h && att_src && att_dst && a_src && a_dst, "dc_gat_alpha_heads_fwd: null pointer");
-    const bool v4 = h_group_ok(C) && ldh % 4 == 0 && h_al16(h) && h_al16(att_src) && h_al16(att_dst);
+    const bool v4 = h_group_ok(C) && ldh % 4 == 0 && al16(h) && al16(att_src) && al16(att_dst);
     const dim3 grid((unsigned)((N + 3) / 4));
     if (v4)
         DC_LAUNCH(k_gat_alpha_heads_fwd_v4, grid, dim3(256), 0, stream, h, ldh, att_src, att_dst, a_src, a_dst, N, (int)H,
@@ -558,7 +523,7 @@ extern "C" int dc_spmm_f32_heads_bias_act(const int32_t *ptr, const int32_t *oth
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && alpha && x && y, "dc_spmm_f32_heads_bias_act: null pointer");
     DC_REQUIRE(x != y, "dc_spmm_f32_heads_bias_act: y must not alias x");
-    const bool vec4 = C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && h_al16(x) && h_al16(y) && (!bias || h_al16(bias));
+    const bool vec4 = C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(y) && (!bias || al16(bias));
     const dim3 grid((unsigned)((N + 3) / 4));
 #define DC_SPMM_HEADS(VEC, MEAN)                                                                                   \
     DC_LAUNCH((k_spmm_heads<VEC, 8, MEAN>), grid, dim3(256), 0, stream, ptr, other, alpha, x, ldx, bias, relu, y, ldy, N, \
@@ -578,7 +543,7 @@ extern "C" int dc_sddmm_f32_heads(const int32_t *ptr, const int32_t *other, cons
     DC_REQUIRE(ldg >= H * C && ldh >= H * C, "dc_sddmm_f32_heads: leading dimension smaller than H * C");
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && g && h && d, "dc_sddmm_f32_heads: null pointer");
-    const bool v4 = h_group_ok(C) && ldg % 4 == 0 && ldh % 4 == 0 && h_al16(g) && h_al16(h);
+    const bool v4 = h_group_ok(C) && ldg % 4 == 0 && ldh % 4 == 0 && al16(g) && al16(h);
     const dim3 grid((unsigned)((N + 3) / 4));
     if (v4)
         DC_LAUNCH((k_sddmm_heads_v4<4>), grid, dim3(256), 0, stream, ptr, other, g, ldg, h, ldh, d, N, (int)H, (int)C);
@@ -627,10 +592,10 @@ extern "C" int dc_gat_alpha_heads_bwd(const float *h, int64_t ldh, const float *
     hipStream_t stream = (hipStream_t)stream_;
     DC_HEADS_SHAPE("dc_gat_alpha_heads_bwd", N, H, C);
     const int64_t F = H * C;
-    DC_REQUIRE(h_width_ok(F), "dc_gat_alpha_heads_bwd: H * C must be a multiple of 4 that divides 1024 (H*C=%lld)",
+    DC_REQUIRE(colsum_width_ok(F), "dc_gat_alpha_heads_bwd: H * C must be a multiple of 4 that divides 1024 (H*C=%lld)",
                (long long)F);
     DC_REQUIRE(h && ga_src && ga_dst && att_src && att_dst && gh && g_att_src && g_att_dst && ldh >= F && ldgh >= F &&
-                   ldh % 4 == 0 && ldgh % 4 == 0 && h_al16(h) && h_al16(gh) && h_al16(att_src) && h_al16(att_dst),
+                   ldh % 4 == 0 && ldgh % 4 == 0 && al16(h) && al16(gh) && al16(att_src) && al16(att_dst),
                "dc_gat_alpha_heads_bwd: null / misaligned operand");
     const int64_t nb = (N + kEpiRowsH - 1) / kEpiRowsH;
     DC_REQUIRE(workspace_bytes >= nb * F * 2 * (int64_t)sizeof(float) && (workspace || nb == 0),

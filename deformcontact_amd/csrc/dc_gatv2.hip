@@ -9,12 +9,13 @@
 // gather H*C floats per edge.  Per-edge vectors are EDGE-MAJOR [capacity, H] as in dc_gat_heads.hip, whose aggregation
 // (dc_spmm_f32_heads_bias_act) and SDDMM (dc_sddmm_f32_heads) the layer uses unchanged.
 //
-// Rules of dc_gat_heads.hip: destination-sorted segments, every sum in a fixed order, products and sums rounded
-// separately, no float atomics, no host read - two runs give the same bits.  The long sums (a segment's softmax
+// Rules of the segment kernels (the order-defining helpers: see dc_segment.h): destination-sorted segments, every sum
+// in a fixed order, products and sums rounded separately, no float atomics, no host read - two runs give the same bits.
+// The long sums (a segment's softmax
 // denominator, the per-column sums over a segment's edges) are compensated (Kahan): a hub with thousands of edges
 // costs no more digits than a short segment.  Any H >= 1, C >= 1 and in-degree, N = 0: no width cap - what a lane
 // cannot hold in registers it reads again (forward) or works through in column chunks (backward).
-#include "dc_common.h"
+#include "dc_segment.h"
 
 #pragma clang fp contract(off)
 
@@ -22,32 +23,11 @@ namespace dc {
 
 namespace {
 
-template <int VEC> struct VecV2;
-template <> struct VecV2<1> { using T = float; };
-template <> struct VecV2<4> { using T = float4; };
-
-__device__ __forceinline__ float v2_lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
 __device__ __forceinline__ float v2_dlrelu(float v, float slope) { return v > 0.f ? 1.0f : slope; }
-
-// compensated running sum: (acc, cmp) += v, in the order of the calls
-__device__ __forceinline__ void v2_kahan(float &acc, float &cmp, float v) {
-    const float y = v - cmp;
-    const float t = acc + y;
-    cmp = (t - acc) - y;
-    acc = t;
-}
-
-__device__ __forceinline__ float v2_zero(float) { return 0.0f; }
-__device__ __forceinline__ float4 v2_zero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-template <class V>
-__device__ __forceinline__ V v2_load(const float *p, bool ok) {
-    return ok ? *reinterpret_cast<const V *>(p) : v2_zero(V{});
-}
 
 // acc += sum over the lane's channels of att * leaky_relu(xl + xr), channel order
 __device__ __forceinline__ void v2_score(float &acc, float xl, float xr, float att, float slope) {
-    const float m = att * v2_lrelu(xl + xr, slope);
+    const float m = att * lrelu(xl + xr, slope);
     acc = acc + m;
 }
 __device__ __forceinline__ void v2_score(float &acc, const float4 &xl, const float4 &xr, const float4 &att, float slope) {
@@ -55,31 +35,6 @@ __device__ __forceinline__ void v2_score(float &acc, const float4 &xl, const flo
     v2_score(acc, xl.y, xr.y, att.y, slope);
     v2_score(acc, xl.z, xr.z, att.z, slope);
     v2_score(acc, xl.w, xr.w, att.w, slope);
-}
-
-// sum over aligned groups of T lanes (T a power of two <= 64), fixed butterfly: every lane of the group gets the sum
-__device__ __forceinline__ float v2_group_sum(float v, int T) {
-    for (int d = T >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-
-// per-column state of the backward kernels: VEC columns of one head per lane and unit
-template <int VEC> struct ColsV2 { float a[VEC]; };
-template <int VEC>
-__device__ __forceinline__ ColsV2<VEC> v2_cols(const float *p, bool ok) {
-    ColsV2<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 v = v2_load<float4>(p, ok);
-        r.a[0] = v.x, r.a[1] = v.y, r.a[2] = v.z, r.a[3] = v.w;
-    } else {
-        r.a[0] = ok ? *p : 0.f;
-    }
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ void v2_store(float *p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
 }
 
 }  // namespace
@@ -99,7 +54,7 @@ __global__ void __launch_bounds__(256)
 k_gatv2_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other, const float *__restrict__ xl,
                     int64_t ldxl, const float *__restrict__ xr, int64_t ldxr, const float *__restrict__ att, float slope,
                     float *alpha, int64_t N, int H, int C, int T) {
-    using V = typename VecV2<VEC>::T;
+    using V = typename Vec<VEC>::T;
     constexpr int U = kEdgesV2;
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
     const int64_t row = __builtin_amdgcn_readfirstlane((int)(lb * 4u + (threadIdx.x >> 6)));
@@ -117,8 +72,8 @@ k_gatv2_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
         for (int r = 0; r < kRegV2; ++r) {
             const int cu = sub + T * r;
             const bool ok = hv && cu < Cv;
-            xrr[r] = v2_load<V>(xr + row * ldxr + hcol + cu * VEC, ok);
-            atr[r] = v2_load<V>(att + hcol + cu * VEC, ok);
+            xrr[r] = vec_load<V>(xr + row * ldxr + hcol + cu * VEC, ok);
+            atr[r] = vec_load<V>(att + hcol + cu * VEC, ok);
         }
         float m = -INFINITY;
         for (int p = beg; p < end; p += U) {
@@ -137,7 +92,7 @@ k_gatv2_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
                     const bool ok = hv && cu < Cv;
                     V v[U];
 #pragma unroll
-                    for (int u = 0; u < U; ++u) v[u] = v2_load<V>(xl + s[u] * ldxl + hcol + cu * VEC, ok && u < n);
+                    for (int u = 0; u < U; ++u) v[u] = vec_load<V>(xl + s[u] * ldxl + hcol + cu * VEC, ok && u < n);
 #pragma unroll
                     for (int u = 0; u < U; ++u) v2_score(acc[u], v[u], xrr[r], atr[r], slope);
                 }
@@ -145,18 +100,18 @@ k_gatv2_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
             for (int r = kRegV2; r < J; ++r) {                 // heads wider than the registers hold: xr, att read again
                 const int cu = sub + T * r;
                 const bool ok = hv && cu < Cv;
-                const V xv = v2_load<V>(xr + row * ldxr + hcol + cu * VEC, ok);
-                const V av = v2_load<V>(att + hcol + cu * VEC, ok);
+                const V xv = vec_load<V>(xr + row * ldxr + hcol + cu * VEC, ok);
+                const V av = vec_load<V>(att + hcol + cu * VEC, ok);
                 V v[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) v[u] = v2_load<V>(xl + s[u] * ldxl + hcol + cu * VEC, ok && u < n);
+                for (int u = 0; u < U; ++u) v[u] = vec_load<V>(xl + s[u] * ldxl + hcol + cu * VEC, ok && u < n);
 #pragma unroll
                 for (int u = 0; u < U; ++u) v2_score(acc[u], v[u], xv, av, slope);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (u < n) {                                   // wave-uniform
-                    const float e = v2_group_sum(acc[u], T);
+                    const float e = group_sum(acc[u], T);
                     m = fmaxf(m, e);
                     if (hv && sub == 0) alpha[(int64_t)(p + u) * H + k] = e;
                 }
@@ -167,7 +122,7 @@ k_gatv2_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
                 float *al = alpha + (int64_t)p * H + k;
                 const float ex = expf(*al - m);
                 *al = ex;
-                v2_kahan(sum, cmp, ex);
+                kahan_add(sum, cmp, ex);
             }
             const float den = sum + 1e-16f;
             for (int p = beg; p < end; ++p) {
@@ -183,12 +138,6 @@ k_gatv2_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
 // k_gat_softmax_heads_bwd (dc_gat_heads.hip): kSubV2 lanes per segment, lane `sub` walks edges beg + sub, + kSubV2, ...
 // with HB heads of each edge in registers.
 constexpr int kSubV2 = 8;
-
-__device__ __forceinline__ float subv2_sum(float v) {
-#pragma unroll
-    for (int d = kSubV2 / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
 
 template <int HB>
 __global__ void __launch_bounds__(256)
@@ -206,10 +155,10 @@ k_gatv2_logit_grad(const int32_t *__restrict__ ptr, const float *__restrict__ al
             const float *al = alpha + (int64_t)p * H + k0, *ga = galpha + (int64_t)p * H + k0;
 #pragma unroll
             for (int b = 0; b < HB; ++b)
-                if (k0 + b < H) v2_kahan(dot[b], cmp[b], al[b] * ga[b]);
+                if (k0 + b < H) kahan_add(dot[b], cmp[b], al[b] * ga[b]);
         }
 #pragma unroll
-        for (int b = 0; b < HB; ++b) dot[b] = subv2_sum(dot[b]);
+        for (int b = 0; b < HB; ++b) dot[b] = sub_sum<kSubV2>(dot[b]);
         for (int p = beg + sub; p < end; p += kSubV2) {
             const float *al = alpha + (int64_t)p * H + k0, *ga = galpha + (int64_t)p * H + k0;
             float *o = ge + (int64_t)p * H + k0;
@@ -244,7 +193,7 @@ k_gatv2_dst_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
     for (int u0 = 0; u0 < Fv; u0 += R * kWave) {               // uniform over the workgroup
         bool ok[R];
         int col[R], kk[R];
-        ColsV2<VEC> av[R];
+        Cols<VEC> av[R];
         float ga[R][VEC], gc[R][VEC];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -252,17 +201,17 @@ k_gatv2_dst_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
             ok[r] = u < Fv;
             col[r] = ok[r] ? u * VEC : 0;
             kk[r] = col[r] / C;
-            av[r] = v2_cols<VEC>(att + col[r], ok[r]);
+            av[r] = cols_load<VEC>(att + col[r], ok[r]);
 #pragma unroll
             for (int q = 0; q < VEC; ++q) ga[r][q] = 0.f, gc[r][q] = 0.f;
         }
         for (int64_t row = r0 + wave; row < r1; row += 4) {
             const int beg = ptr[row], end = ptr[row + 1];
-            ColsV2<VEC> xv[R];
+            Cols<VEC> xv[R];
             float acc[R][VEC], cmp[R][VEC];
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                xv[r] = v2_cols<VEC>(xr + row * ldxr + col[r], ok[r]);
+                xv[r] = cols_load<VEC>(xr + row * ldxr + col[r], ok[r]);
 #pragma unroll
                 for (int q = 0; q < VEC; ++q) acc[r][q] = 0.f, cmp[r][q] = 0.f;
             }
@@ -273,12 +222,12 @@ k_gatv2_dst_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
                 for (int u = 0; u < U; ++u) s[u] = u < n ? other[p + u] : row;
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    ColsV2<VEC> v[U];
+                    Cols<VEC> v[U];
                     float g[U];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const bool on = ok[r] && u < n;
-                        v[u] = v2_cols<VEC>(xl + s[u] * ldxl + col[r], on);
+                        v[u] = cols_load<VEC>(xl + s[u] * ldxl + col[r], on);
                         g[u] = on ? ge[(int64_t)(p + u) * H + kk[r]] : 0.f;
                     }
 #pragma unroll
@@ -288,15 +237,15 @@ k_gatv2_dst_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
                             for (int q = 0; q < VEC; ++q) {
                                 const float sv = v[u].a[q] + xv[r].a[q];
                                 const float ga_t = g[u] * av[r].a[q];
-                                v2_kahan(acc[r][q], cmp[r][q], ga_t * v2_dlrelu(sv, slope));
-                                v2_kahan(ga[r][q], gc[r][q], g[u] * v2_lrelu(sv, slope));
+                                kahan_add(acc[r][q], cmp[r][q], ga_t * v2_dlrelu(sv, slope));
+                                kahan_add(ga[r][q], gc[r][q], g[u] * lrelu(sv, slope));
                             }
                         }
                 }
             }
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                if (ok[r]) v2_store<VEC>(g_xr + row * ldg + col[r], acc[r]);
+                if (ok[r]) cols_store<VEC>(g_xr + row * ldg + col[r], acc[r]);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -313,7 +262,7 @@ k_gatv2_dst_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
                         const int x = (r * kWave + lane) * VEC + q;
                         t[q] = ((red[0][x] + red[1][x]) + red[2][x]) + red[3][x];
                     }
-                    v2_store<VEC>(partial + (int64_t)blockIdx.x * F + col[r], t);
+                    cols_store<VEC>(partial + (int64_t)blockIdx.x * F + col[r], t);
                 }
         }
         __syncthreads();
@@ -355,7 +304,7 @@ k_gatv2_src_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
     for (int u0 = 0; u0 < Fv; u0 += R * kWave) {
         bool ok[R];
         int col[R], kk[R];
-        ColsV2<VEC> av[R], xv[R];
+        Cols<VEC> av[R], xv[R];
         float acc[R][VEC], cmp[R][VEC];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -363,8 +312,8 @@ k_gatv2_src_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
             ok[r] = u < Fv;
             col[r] = ok[r] ? u * VEC : 0;
             kk[r] = col[r] / C;
-            av[r] = v2_cols<VEC>(att + col[r], ok[r]);
-            xv[r] = v2_cols<VEC>(xl + row * ldxl + col[r], ok[r]);
+            av[r] = cols_load<VEC>(att + col[r], ok[r]);
+            xv[r] = cols_load<VEC>(xl + row * ldxl + col[r], ok[r]);
 #pragma unroll
             for (int q = 0; q < VEC; ++q) acc[r][q] = 0.f, cmp[r][q] = 0.f;
         }
@@ -378,13 +327,13 @@ k_gatv2_src_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
             }
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                ColsV2<VEC> g[U], v[U];
+                Cols<VEC> g[U], v[U];
                 float a[U], e[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const bool on = ok[r] && u < n;
-                    g[u] = v2_cols<VEC>(gm + s[u] * ldgm + col[r], on);
-                    v[u] = v2_cols<VEC>(xr + s[u] * ldxr + col[r], on);
+                    g[u] = cols_load<VEC>(gm + s[u] * ldgm + col[r], on);
+                    v[u] = cols_load<VEC>(xr + s[u] * ldxr + col[r], on);
                     a[u] = on ? alpha[f[u] * H + kk[r]] : 0.f;
                     e[u] = on ? ge[f[u] * H + kk[r]] : 0.f;
                 }
@@ -397,26 +346,15 @@ k_gatv2_src_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
                             const float m = a[u] * g[u].a[q];
                             const float ea = e[u] * av[r].a[q];
                             const float t = ea * v2_dlrelu(sv, slope);
-                            v2_kahan(acc[r][q], cmp[r][q], m + t);
+                            kahan_add(acc[r][q], cmp[r][q], m + t);
                         }
                     }
             }
         }
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            if (ok[r]) v2_store<VEC>(g_xl + row * ldg + col[r], acc[r]);
+            if (ok[r]) cols_store<VEC>(g_xl + row * ldg + col[r], acc[r]);
     }
-}
-
-static inline bool v2_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-static inline bool v2_sizes_ok(int64_t N, int64_t H, int64_t C) {
-    return N < (int64_t)INT32_MAX / 4 && H < (1 << 16) && C < (1 << 24) && H * C < (1 << 24);
-}
-// lanes per head of the forward kernel: the power of two >= units, at most one wave
-static inline int v2_lanes_per_head(int64_t units) {
-    int t = 1;
-    while (t < kWave && t < units) t <<= 1;
-    return t;
 }
 
 }  // namespace dc
@@ -426,7 +364,7 @@ using namespace dc;
 #define DC_GATV2_SHAPE(name, N, H, C)                                                                              \
     DC_REQUIRE((N) >= 0 && (H) >= 1 && (C) >= 1, name ": need N >= 0, H >= 1, C >= 1 (N=%lld H=%lld C=%lld)",     \
                (long long)(N), (long long)(H), (long long)(C));                                                    \
-    DC_REQUIRE(v2_sizes_ok(N, H, C), name ": size out of range")
+    DC_REQUIRE(sizes_ok(N, H, C), name ": size out of range")
 
 extern "C" int dc_gatv2_softmax_fwd(const int32_t *ptr, const int32_t *other, const float *xl, int64_t ldxl,
                                     const float *xr, int64_t ldxr, const float *att, float slope, float *alpha, int64_t N,
@@ -436,19 +374,19 @@ extern "C" int dc_gatv2_softmax_fwd(const int32_t *ptr, const int32_t *other, co
     DC_REQUIRE(ldxl >= H * C && ldxr >= H * C, "dc_gatv2_softmax_fwd: leading dimension smaller than H * C");
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && xl && xr && att && alpha, "dc_gatv2_softmax_fwd: null pointer");
-    const bool v4 = C % 4 == 0 && ldxl % 4 == 0 && ldxr % 4 == 0 && v2_al16(xl) && v2_al16(xr) && v2_al16(att);
+    const bool v4 = C % 4 == 0 && ldxl % 4 == 0 && ldxr % 4 == 0 && al16(xl) && al16(xr) && al16(att);
     const dim3 grid((unsigned)((N + 3) / 4));
     if (v4)
         DC_LAUNCH((k_gatv2_softmax_fwd<4>), grid, dim3(256), 0, stream, ptr, other, xl, ldxl, xr, ldxr, att, slope, alpha,
-                  N, (int)H, (int)C, v2_lanes_per_head(C / 4));
+                  N, (int)H, (int)C, lanes_per_head(C / 4));
     else
         DC_LAUNCH((k_gatv2_softmax_fwd<1>), grid, dim3(256), 0, stream, ptr, other, xl, ldxl, xr, ldxr, att, slope, alpha,
-                  N, (int)H, (int)C, v2_lanes_per_head(C));
+                  N, (int)H, (int)C, lanes_per_head(C));
     return check_launch("dc_gatv2_softmax_fwd");
 }
 
 extern "C" int64_t dc_gatv2_workspace_bytes(int64_t N, int64_t H, int64_t C) {
-    if (N < 0 || H < 1 || C < 1 || !v2_sizes_ok(N, H, C)) return -1;
+    if (N < 0 || H < 1 || C < 1 || !sizes_ok(N, H, C)) return -1;
     return (N + kRowsV2 - 1) / kRowsV2 * H * C * (int64_t)sizeof(float);
 }
 
@@ -473,8 +411,8 @@ extern "C" int dc_gatv2_softmax_bwd(const int32_t *ptr, const int32_t *other, co
         else if (H == 2) DC_LAUNCH((k_gatv2_logit_grad<2>), grid_e, dim3(256), 0, stream, ptr, alpha, galpha, ge, N, (int)H);
         else if (H <= 4) DC_LAUNCH((k_gatv2_logit_grad<4>), grid_e, dim3(256), 0, stream, ptr, alpha, galpha, ge, N, (int)H);
         else DC_LAUNCH((k_gatv2_logit_grad<8>), grid_e, dim3(256), 0, stream, ptr, alpha, galpha, ge, N, (int)H);
-        const bool v4 = C % 4 == 0 && ldxl % 4 == 0 && ldxr % 4 == 0 && ldg % 4 == 0 && v2_al16(xl) && v2_al16(xr) &&
-                        v2_al16(att) && v2_al16(g_xr) && v2_al16(workspace);
+        const bool v4 = C % 4 == 0 && ldxl % 4 == 0 && ldxr % 4 == 0 && ldg % 4 == 0 && al16(xl) && al16(xr) &&
+                        al16(att) && al16(g_xr) && al16(workspace);
         if (v4)
             DC_LAUNCH((k_gatv2_dst_bwd<4>), dim3((unsigned)nb), dim3(256), 0, stream, ptr, other, ge, xl, ldxl, xr, ldxr,
                       att, slope, g_xr, ldg, (float *)workspace, N, (int)H, (int)C);
@@ -500,8 +438,8 @@ extern "C" int dc_gatv2_source_bwd(const int32_t *ptr_t, const int32_t *other_t,
     DC_REQUIRE(ptr_t && other_t && to_fwd && alpha && ge && gm && xl && xr && att && g_xl,
                "dc_gatv2_source_bwd: null pointer");
     DC_REQUIRE(g_xl != xl && g_xl != xr && g_xl != gm, "dc_gatv2_source_bwd: g_xl must not alias xl / xr / gm");
-    const bool v4 = C % 4 == 0 && ldgm % 4 == 0 && ldxl % 4 == 0 && ldxr % 4 == 0 && ldg % 4 == 0 && v2_al16(gm) &&
-                    v2_al16(xl) && v2_al16(xr) && v2_al16(att) && v2_al16(g_xl);
+    const bool v4 = C % 4 == 0 && ldgm % 4 == 0 && ldxl % 4 == 0 && ldxr % 4 == 0 && ldg % 4 == 0 && al16(gm) &&
+                    al16(xl) && al16(xr) && al16(att) && al16(g_xl);
     const dim3 grid((unsigned)((N + 3) / 4));
     if (v4)
         DC_LAUNCH((k_gatv2_src_bwd<4>), grid, dim3(256), 0, stream, ptr_t, other_t, to_fwd, alpha, ge, gm, ldgm, xl, ldxl, xr,

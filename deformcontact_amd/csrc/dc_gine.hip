@@ -20,68 +20,22 @@
 // every row of g_e is written exactly once, by one lane group.  An edge with an endpoint outside [0, N) - the build
 // skips and flags those - gets a zero row.
 //
-// Rules of dc_sage.hip: fp contract(off), every sum in a fixed order, no float atomics, no host read - two runs give
-// the same bits, and every entry can be captured.  Any F >= 1: 16-byte loads where F % 4 == 0 and every pointer and
-// stride allows it, scalar loads otherwise; no width cap (columns in chunks of the lane group); any in-degree.
+// Rules of the segment kernels (helpers: see dc_segment.h): fp contract(off), every sum in a fixed order, no float
+// atomics, no host read - two runs give the same bits, and every entry can be captured.  Any F >= 1: 16-byte loads
+// where F % 4 == 0 and every pointer and stride allows it, scalar loads otherwise; no width cap (columns in chunks of
+// the lane group); any in-degree.
 //
-// Lanes as there: a row (of x, or of e for g_e) is served by a group of L lanes, L the power of two >= F / VEC within
-// 4..64; 256 / L rows per workgroup; L = 64 is the one-wave-per-row form (row, segment bounds and ids wave-uniform).
+// Lanes as in dc_sage.hip (seg_row, dc_segment.h): a row (of x, or of e for g_e) is served by a group of L lanes, L the
+// power of two >= F / VEC within 4..64; 256 / L rows per workgroup; L = 64 is the one-wave-per-row form (row, segment bounds and ids wave-uniform).
 // U edges are in flight per lane before the first is consumed (two gathered rows per edge: U = 4).  No lane reads what
 // another lane wrote and there is no cross-lane step.
-#include "dc_common.h"
+#include "dc_segment.h"
 
 #pragma clang fp contract(off)
 
 namespace dc {
 
-namespace {
-
 constexpr int kEdgesGn = 4;        // edges in flight per lane: two gathered rows per edge (x / g_y and e)
-
-template <int VEC> struct ColsGn { float a[VEC]; };
-
-template <int VEC>
-__device__ __forceinline__ ColsGn<VEC> gn_load(const float *p, bool ok) {
-    ColsGn<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 v = ok ? *reinterpret_cast<const float4 *>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-        r.a[0] = v.x, r.a[1] = v.y, r.a[2] = v.z, r.a[3] = v.w;
-    } else {
-        r.a[0] = ok ? *p : 0.f;
-    }
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ void gn_store(float *p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
-
-// compensated running sum: (acc, cmp) += v, in the order of the calls
-__device__ __forceinline__ void gn_kahan(float &acc, float &cmp, float v) {
-    const float y = v - cmp;
-    const float t = acc + y;
-    cmp = (t - acc) - y;
-    acc = t;
-}
-
-// the row this lane works for and its place in the row's lane group (lg = log2 L; WAVE: L = 64, row wave-uniform)
-template <bool WAVE>
-__device__ __forceinline__ bool gn_row(int lg, int64_t rows, int64_t &row, int &sub, int &L) {
-    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-    if constexpr (WAVE) {
-        row = __builtin_amdgcn_readfirstlane((int)(lb * 4u + (threadIdx.x >> 6)));
-        sub = threadIdx.x & 63;
-        L = kWave;
-    } else {
-        L = 1 << lg;
-        row = (int64_t)lb * (256 >> lg) + (threadIdx.x >> lg);
-        sub = threadIdx.x & (L - 1);
-    }
-    return row < rows;
-}
-
-}  // namespace
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 template <int VEC, bool WAVE>
@@ -92,7 +46,7 @@ k_gine_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other, c
     constexpr int U = kEdgesGn;
     int64_t row;
     int sub, L;
-    if (!gn_row<WAVE>(lg, N, row, sub, L)) return;
+    if (!seg_row<WAVE>(lg, N, row, sub, L)) return;
     const int beg = ptr[row], end = ptr[row + 1];
     const float ope = eps ? 1.f + *eps : 0.f;
     for (int c = sub * VEC; c < F; c += L * VEC) {
@@ -102,7 +56,7 @@ k_gine_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other, c
         for (int p = beg; p < end; p += U) {
             const int n = end - p;
             int64_t s[U], q[U];
-            ColsGn<VEC> xv[U], ev[U];
+            Cols<VEC> xv[U], ev[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 s[u] = u < n ? other[p + u] : row;
@@ -110,8 +64,8 @@ k_gine_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other, c
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                xv[u] = gn_load<VEC>(x + s[u] * ldx + c, u < n);
-                ev[u] = gn_load<VEC>(e + q[u] * lde + c, u < n);
+                xv[u] = cols_load<VEC>(x + s[u] * ldx + c, u < n);
+                ev[u] = cols_load<VEC>(e + q[u] * lde + c, u < n);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -124,14 +78,14 @@ k_gine_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other, c
                 }
         }
         if (eps) {
-            const ColsGn<VEC> xi = gn_load<VEC>(x + row * ldx + c, true);
+            const Cols<VEC> xi = cols_load<VEC>(x + row * ldx + c, true);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 const float r = ope * xi.a[k];
                 acc[k] = r + acc[k];
             }
         }
-        gn_store<VEC>(y + row * ldy + c, acc);
+        cols_store<VEC>(y + row * ldy + c, acc);
     }
 }
 
@@ -145,18 +99,18 @@ k_gine_bwd_x(const int32_t *__restrict__ ptr_t, const int32_t *__restrict__ othe
     constexpr int U = kEdgesGn;
     int64_t row;
     int sub, L;
-    if (!gn_row<WAVE>(lg, N, row, sub, L)) return;
+    if (!seg_row<WAVE>(lg, N, row, sub, L)) return;
     const int beg = ptr_t[row], end = ptr_t[row + 1];
     const float ope = eps ? 1.f + *eps : 0.f;
     for (int c = sub * VEC; c < F; c += L * VEC) {
-        const ColsGn<VEC> xj = gn_load<VEC>(x + row * ldx + c, true);
+        const Cols<VEC> xj = cols_load<VEC>(x + row * ldx + c, true);
         float acc[VEC], cmp[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = 0.f, cmp[k] = 0.f;
         for (int p = beg; p < end; p += U) {
             const int n = end - p;
             int64_t d[U], q[U];
-            ColsGn<VEC> gv[U], ev[U];
+            Cols<VEC> gv[U], ev[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 d[u] = u < n ? other_t[p + u] : row;
@@ -164,8 +118,8 @@ k_gine_bwd_x(const int32_t *__restrict__ ptr_t, const int32_t *__restrict__ othe
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                gv[u] = gn_load<VEC>(gy + d[u] * ldgy + c, u < n);
-                ev[u] = gn_load<VEC>(e + q[u] * lde + c, u < n);
+                gv[u] = cols_load<VEC>(gy + d[u] * ldgy + c, u < n);
+                ev[u] = cols_load<VEC>(e + q[u] * lde + c, u < n);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -173,19 +127,19 @@ k_gine_bwd_x(const int32_t *__restrict__ ptr_t, const int32_t *__restrict__ othe
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) {
                         const float m = xj.a[k] + ev[u].a[k];
-                        gn_kahan(acc[k], cmp[k], m > 0.f ? gv[u].a[k] : 0.f);
+                        kahan_add(acc[k], cmp[k], m > 0.f ? gv[u].a[k] : 0.f);
                     }
                 }
         }
         if (eps) {
-            const ColsGn<VEC> gj = gn_load<VEC>(gy + row * ldgy + c, true);
+            const Cols<VEC> gj = cols_load<VEC>(gy + row * ldgy + c, true);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 const float r = ope * gj.a[k];
                 acc[k] = r + acc[k];
             }
         }
-        gn_store<VEC>(gx + row * ldgx + c, acc);
+        cols_store<VEC>(gx + row * ldgx + c, acc);
     }
 }
 
@@ -197,30 +151,21 @@ k_gine_bwd_e(const int64_t *__restrict__ src, const int64_t *__restrict__ dst, c
              float *__restrict__ ge, int64_t ldge, int64_t N, int64_t E, int F, int lg) {
     int64_t q;
     int sub, L;
-    if (!gn_row<WAVE>(lg, E, q, sub, L)) return;
+    if (!seg_row<WAVE>(lg, E, q, sub, L)) return;
     const int64_t j = src[q], i = dst[q];
     const bool ok = j >= 0 && j < N && i >= 0 && i < N;          // (an edge the build skipped: a zero row)
     for (int c = sub * VEC; c < F; c += L * VEC) {
-        const ColsGn<VEC> xv = gn_load<VEC>(x + j * ldx + c, ok);
-        const ColsGn<VEC> ev = gn_load<VEC>(e + q * lde + c, ok);
-        const ColsGn<VEC> gv = gn_load<VEC>(gy + i * ldgy + c, ok);
+        const Cols<VEC> xv = cols_load<VEC>(x + j * ldx + c, ok);
+        const Cols<VEC> ev = cols_load<VEC>(e + q * lde + c, ok);
+        const Cols<VEC> gv = cols_load<VEC>(gy + i * ldgy + c, ok);
         float out[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             const float m = xv.a[k] + ev.a[k];
             out[k] = ok && m > 0.f ? gv.a[k] : 0.f;
         }
-        gn_store<VEC>(ge + q * ldge + c, out);
+        cols_store<VEC>(ge + q * ldge + c, out);
     }
-}
-
-static inline bool gn_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-static inline bool gn_sizes_ok(int64_t rows, int64_t F) { return rows < (int64_t)INT32_MAX / 4 && F < (1 << 24); }
-// log2 of the lanes per row: the power of two >= units within 4..64
-static inline int gn_log2_lanes(int64_t units) {
-    int lg = 2;
-    while (lg < 6 && (1 << lg) < units) ++lg;
-    return lg;
 }
 
 }  // namespace dc
@@ -229,12 +174,12 @@ using namespace dc;
 
 #define DC_GINE_SHAPE(name, N, F)                                                                                  \
     DC_REQUIRE((N) >= 0 && (F) >= 1, name ": need N >= 0, F >= 1 (N=%lld F=%lld)", (long long)(N), (long long)(F)); \
-    DC_REQUIRE(gn_sizes_ok(N, F), name ": size out of range")
+    DC_REQUIRE(sizes_ok(N, F), name ": size out of range")
 
 // the four forms of a kernel: 16-byte or scalar columns, one wave per row or 64 / L rows per wave (ROWS rows in all)
 #define DC_GINE_LAUNCH(kernel, v4, ROWS, F, stream, ...)                                                           \
     do {                                                                                                           \
-        const int lg_ = gn_log2_lanes((v4) ? (F) / 4 : (F));                                                       \
+        const int lg_ = log2_lanes((v4) ? (F) / 4 : (F));                                                       \
         const int64_t rows_ = 256 >> lg_;                                                                          \
         const dim3 grid_((unsigned)(((ROWS) + rows_ - 1) / rows_));                                                \
         if ((v4) && lg_ == 6) DC_LAUNCH((kernel<4, true>), grid_, dim3(256), 0, stream, __VA_ARGS__, (int)(F), lg_); \
@@ -252,7 +197,7 @@ extern "C" int dc_gine_fwd(const int32_t *ptr, const int32_t *other, const int32
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && perm && x && e && y, "dc_gine_fwd: null pointer");
     DC_REQUIRE(y != x && y != e, "dc_gine_fwd: y must not alias x or e");
-    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && lde % 4 == 0 && ldy % 4 == 0 && gn_al16(x) && gn_al16(e) && gn_al16(y);
+    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && lde % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(e) && al16(y);
     DC_GINE_LAUNCH(k_gine_fwd, v4, N, F, stream, ptr, other, perm, x, ldx, e, lde, eps, y, ldy, N);
     return check_launch("dc_gine_fwd");
 }
@@ -266,8 +211,8 @@ extern "C" int dc_gine_bwd_x(const int32_t *ptr_t, const int32_t *other_t, const
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr_t && other_t && perm_t && x && e && gy && gx, "dc_gine_bwd_x: null pointer");
     DC_REQUIRE(gx != x && gx != e && gx != gy, "dc_gine_bwd_x: gx must not alias an input");
-    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && lde % 4 == 0 && ldgy % 4 == 0 && ldgx % 4 == 0 && gn_al16(x) &&
-                    gn_al16(e) && gn_al16(gy) && gn_al16(gx);
+    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && lde % 4 == 0 && ldgy % 4 == 0 && ldgx % 4 == 0 && al16(x) &&
+                    al16(e) && al16(gy) && al16(gx);
     DC_GINE_LAUNCH(k_gine_bwd_x, v4, N, F, stream, ptr_t, other_t, perm_t, x, ldx, e, lde, eps, gy, ldgy, gx, ldgx, N);
     return check_launch("dc_gine_bwd_x");
 }
@@ -277,13 +222,13 @@ extern "C" int dc_gine_bwd_e(const int64_t *src, const int64_t *dst, const float
                              int64_t F, dc_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     DC_GINE_SHAPE("dc_gine_bwd_e", N, F);
-    DC_REQUIRE(E >= 0 && gn_sizes_ok(E, F), "dc_gine_bwd_e: E out of range (E=%lld)", (long long)E);
+    DC_REQUIRE(E >= 0 && sizes_ok(E, F), "dc_gine_bwd_e: E out of range (E=%lld)", (long long)E);
     DC_REQUIRE(ldx >= F && lde >= F && ldgy >= F && ldge >= F, "dc_gine_bwd_e: leading dimension smaller than F");
     if (E == 0) return DC_OK;
     DC_REQUIRE(src && dst && x && e && gy && ge, "dc_gine_bwd_e: null pointer");
     DC_REQUIRE(ge != x && ge != e && ge != gy, "dc_gine_bwd_e: ge must not alias an input");
-    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && lde % 4 == 0 && ldgy % 4 == 0 && ldge % 4 == 0 && gn_al16(x) &&
-                    gn_al16(e) && gn_al16(gy) && gn_al16(ge);
+    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && lde % 4 == 0 && ldgy % 4 == 0 && ldge % 4 == 0 && al16(x) &&
+                    al16(e) && al16(gy) && al16(ge);
     DC_GINE_LAUNCH(k_gine_bwd_e, v4, E, F, stream, src, dst, x, ldx, e, lde, gy, ldgy, ge, ldge, N, E);
     return check_launch("dc_gine_bwd_e");
 }

@@ -9,7 +9,7 @@
 //   dc_gat_alpha_fwd / _bwd             both attention dot products in one pass over h; their backward (rank-one
 //                                       updates of dh, the two attention-vector gradients) in one pass
 // Column sums are deterministic: per-block partials combined in block order (no float atomics).
-#include "dc_common.h"
+#include "dc_segment.h"
 
 #pragma clang fp contract(off)
 
@@ -127,9 +127,6 @@ k_gat_alpha_bwd(const float *__restrict__ h, int64_t ldh, const float *__restric
     }
 }
 
-static inline bool epi_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-static inline bool epi_width_ok(int64_t F) { return F >= 4 && F <= 1024 && F % 4 == 0 && 256 % (F / 4) == 0; }
-
 }  // namespace dc
 
 using namespace dc;
@@ -143,10 +140,10 @@ extern "C" int dc_mask_colsum_f32(const float *g, int64_t ldg, const float *y_ma
                                   int64_t ldgm, int64_t N, int64_t F, void *workspace, int64_t workspace_bytes,
                                   float *colsum, int accumulate, dc_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    DC_REQUIRE(N >= 0 && epi_width_ok(F), "dc_mask_colsum_f32: F must be a multiple of 4 that divides 1024 (F=%lld)",
+    DC_REQUIRE(N >= 0 && colsum_width_ok(F), "dc_mask_colsum_f32: F must be a multiple of 4 that divides 1024 (F=%lld)",
                (long long)F);
-    DC_REQUIRE(g && colsum && ldg >= F && ldg % 4 == 0 && epi_al16(g) && (!y_mask || (ldy >= F && ldy % 4 == 0 && epi_al16(y_mask))) &&
-                   (!gm || (ldgm >= F && ldgm % 4 == 0 && epi_al16(gm))),
+    DC_REQUIRE(g && colsum && ldg >= F && ldg % 4 == 0 && al16(g) && (!y_mask || (ldy >= F && ldy % 4 == 0 && al16(y_mask))) &&
+                   (!gm || (ldgm >= F && ldgm % 4 == 0 && al16(gm))),
                "dc_mask_colsum_f32: null / misaligned operand");
     const int64_t nb = (N + kEpiRows - 1) / kEpiRows;
     DC_REQUIRE(workspace_bytes >= dc_colsum_workspace_bytes(N, F, 1) && (workspace || nb == 0),
@@ -164,7 +161,7 @@ extern "C" int dc_gat_alpha_fwd(const float *h, int64_t ldh, const float *att_sr
     hipStream_t stream = (hipStream_t)stream_;
     DC_REQUIRE(N >= 0 && F >= 4 && F % 4 == 0 && ldh >= F && ldh % 4 == 0, "dc_gat_alpha_fwd: F %% 4 == 0, ldh %% 4 == 0");
     if (N == 0) return DC_OK;
-    DC_REQUIRE(h && att_src && att_dst && a_src && a_dst && epi_al16(h) && epi_al16(att_src) && epi_al16(att_dst),
+    DC_REQUIRE(h && att_src && att_dst && a_src && a_dst && al16(h) && al16(att_src) && al16(att_dst),
                "dc_gat_alpha_fwd: null / misaligned operand");
     DC_LAUNCH(k_gat_alpha_fwd, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, h, ldh, att_src, att_dst, a_src,
               a_dst, N, (int)F);
@@ -176,10 +173,10 @@ extern "C" int dc_gat_alpha_bwd(const float *h, int64_t ldh, const float *ga_src
                                 int64_t F, void *workspace, int64_t workspace_bytes, float *g_att_src,
                                 float *g_att_dst, int accumulate, dc_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    DC_REQUIRE(N >= 0 && epi_width_ok(F), "dc_gat_alpha_bwd: F must be a multiple of 4 that divides 1024 (F=%lld)",
+    DC_REQUIRE(N >= 0 && colsum_width_ok(F), "dc_gat_alpha_bwd: F must be a multiple of 4 that divides 1024 (F=%lld)",
                (long long)F);
     DC_REQUIRE(h && ga_src && ga_dst && att_src && att_dst && gh && g_att_src && g_att_dst && ldh >= F && ldgh >= F &&
-                   ldh % 4 == 0 && ldgh % 4 == 0 && epi_al16(h) && epi_al16(gh) && epi_al16(att_src) && epi_al16(att_dst),
+                   ldh % 4 == 0 && ldgh % 4 == 0 && al16(h) && al16(gh) && al16(att_src) && al16(att_dst),
                "dc_gat_alpha_bwd: null / misaligned operand");
     const int64_t nb = (N + kEpiRows - 1) / kEpiRows;
     DC_REQUIRE(workspace_bytes >= dc_colsum_workspace_bytes(N, F, 2) && (workspace || nb == 0),

@@ -12,15 +12,15 @@
 // the comparison is exact - m is a copy of one of the gathered values - so no index image is kept.  Inputs are taken
 // to be finite: what a NaN does to the maximum, its count and the split is unspecified.
 //
-// Rules of dc_gatv2.hip / dc_transformer.hip: every sum in a fixed order (the backward sums compensated), no float
-// atomics, no host read - two runs give the same bits.  Any F >= 1: 16-byte loads where F % 4 == 0 and every pointer
+// Rules of the segment kernels (helpers: see dc_segment.h): every sum in a fixed order (the backward sums compensated), no
+// float atomics, no host read - two runs give the same bits.  Any F >= 1: 16-byte loads where F % 4 == 0 and every pointer
 // and stride allows it, scalar loads otherwise; no width cap (columns in chunks of the lane group); any in-degree.
 //
 // Lanes: a row is served by a group of L lanes, L the power of two >= F / VEC within 4..64; 256 / L rows per
 // workgroup.  L = 64 is the one-wave-per-row form of the hop (row, segment bounds and ids wave-uniform: scalar loads);
 // narrower rows pack 64 / L rows into a wave as k_spmm_sub does.  U edges are in flight per lane before the first is
 // consumed.  No lane reads what another lane wrote and there is no cross-lane step.
-#include "dc_common.h"
+#include "dc_segment.h"
 
 #pragma clang fp contract(off)
 
@@ -31,20 +31,8 @@ namespace {
 constexpr int kEdgesSg = 8;        // rows in flight per lane: one gathered array per edge (mean, max forward)
 constexpr int kEdgesSgBwd = 4;     // the max backward gathers three arrays per edge
 
-template <int VEC> struct ColsSg { float a[VEC]; };
+// the count image of the max: Cols / cols_load / cols_store (dc_segment.h) for int32, an absent element reads as 1
 template <int VEC> struct IntsSg { int a[VEC]; };
-
-template <int VEC>
-__device__ __forceinline__ ColsSg<VEC> sg_load(const float *p, bool ok) {
-    ColsSg<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 v = ok ? *reinterpret_cast<const float4 *>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-        r.a[0] = v.x, r.a[1] = v.y, r.a[2] = v.z, r.a[3] = v.w;
-    } else {
-        r.a[0] = ok ? *p : 0.f;
-    }
-    return r;
-}
 template <int VEC>
 __device__ __forceinline__ IntsSg<VEC> sg_load_i(const int32_t *p, bool ok) {
     IntsSg<VEC> r;
@@ -57,38 +45,9 @@ __device__ __forceinline__ IntsSg<VEC> sg_load_i(const int32_t *p, bool ok) {
     return r;
 }
 template <int VEC>
-__device__ __forceinline__ void sg_store(float *p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
-template <int VEC>
 __device__ __forceinline__ void sg_store_i(int32_t *p, const int (&v)[VEC]) {
     if constexpr (VEC == 4) *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
     else *p = v[0];
-}
-
-// compensated running sum: (acc, cmp) += v, in the order of the calls
-__device__ __forceinline__ void sg_kahan(float &acc, float &cmp, float v) {
-    const float y = v - cmp;
-    const float t = acc + y;
-    cmp = (t - acc) - y;
-    acc = t;
-}
-
-// the row this lane works for and its place in the row's lane group (lg = log2 L; WAVE: L = 64, row wave-uniform)
-template <bool WAVE>
-__device__ __forceinline__ bool sg_row(int lg, int64_t N, int64_t &row, int &sub, int &L) {
-    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-    if constexpr (WAVE) {
-        row = __builtin_amdgcn_readfirstlane((int)(lb * 4u + (threadIdx.x >> 6)));
-        sub = threadIdx.x & 63;
-        L = kWave;
-    } else {
-        L = 1 << lg;
-        row = (int64_t)lb * (256 >> lg) + (threadIdx.x >> lg);
-        sub = threadIdx.x & (L - 1);
-    }
-    return row < N;
 }
 
 }  // namespace
@@ -101,7 +60,7 @@ k_sage_mean_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
     constexpr int U = kEdgesSg;
     int64_t row;
     int sub, L;
-    if (!sg_row<WAVE>(lg, N, row, sub, L)) return;
+    if (!seg_row<WAVE>(lg, N, row, sub, L)) return;
     const int beg = ptr[row], end = ptr[row + 1];
     const float deg = (float)(end - beg);
     for (int c = sub * VEC; c < F; c += L * VEC) {
@@ -111,11 +70,11 @@ k_sage_mean_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
         for (int p = beg; p < end; p += U) {
             const int n = end - p;
             int64_t s[U];
-            ColsSg<VEC> v[U];
+            Cols<VEC> v[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = u < n ? other[p + u] : row;
 #pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = sg_load<VEC>(x + s[u] * ldx + c, u < n);
+            for (int u = 0; u < U; ++u) v[u] = cols_load<VEC>(x + s[u] * ldx + c, u < n);
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (u < n) {
@@ -127,7 +86,7 @@ k_sage_mean_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[k] = acc[k] / deg;
         }
-        sg_store<VEC>(y + row * ldy + c, acc);
+        cols_store<VEC>(y + row * ldy + c, acc);
     }
 }
 
@@ -140,7 +99,7 @@ k_sage_mean_bwd(const int32_t *__restrict__ ptr_t, const int32_t *__restrict__ o
     constexpr int U = kEdgesSg;
     int64_t row;
     int sub, L;
-    if (!sg_row<WAVE>(lg, N, row, sub, L)) return;
+    if (!seg_row<WAVE>(lg, N, row, sub, L)) return;
     const int beg = ptr_t[row], end = ptr_t[row + 1];
     for (int c = sub * VEC; c < F; c += L * VEC) {
         float acc[VEC], cmp[VEC];
@@ -150,22 +109,22 @@ k_sage_mean_bwd(const int32_t *__restrict__ ptr_t, const int32_t *__restrict__ o
             const int n = end - p;
             int64_t s[U];
             float d[U];
-            ColsSg<VEC> v[U];
+            Cols<VEC> v[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = u < n ? other_t[p + u] : row;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 d[u] = u < n ? (float)(ptr[s[u] + 1] - ptr[s[u]]) : 1.f;
-                v[u] = sg_load<VEC>(gy + s[u] * ldgy + c, u < n);
+                v[u] = cols_load<VEC>(gy + s[u] * ldgy + c, u < n);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (u < n) {
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) sg_kahan(acc[k], cmp[k], v[u].a[k] / d[u]);
+                    for (int k = 0; k < VEC; ++k) kahan_add(acc[k], cmp[k], v[u].a[k] / d[u]);
                 }
         }
-        sg_store<VEC>(gx + row * ldgx + c, acc);
+        cols_store<VEC>(gx + row * ldgx + c, acc);
     }
 }
 
@@ -179,7 +138,7 @@ k_sage_max_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ othe
     constexpr int U = kEdgesSg;
     int64_t row;
     int sub, L;
-    if (!sg_row<WAVE>(lg, N, row, sub, L)) return;
+    if (!seg_row<WAVE>(lg, N, row, sub, L)) return;
     const int beg = ptr[row], end = ptr[row + 1];
     for (int c = sub * VEC; c < F; c += L * VEC) {
         float mx[VEC];
@@ -189,11 +148,11 @@ k_sage_max_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ othe
         for (int p = beg; p < end; p += U) {
             const int n = end - p;
             int64_t s[U];
-            ColsSg<VEC> v[U];
+            Cols<VEC> v[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = u < n ? other[p + u] : row;
 #pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = sg_load<VEC>(x + s[u] * ldx + c, u < n);
+            for (int u = 0; u < U; ++u) v[u] = cols_load<VEC>(x + s[u] * ldx + c, u < n);
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (u < n) {
@@ -209,7 +168,7 @@ k_sage_max_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ othe
 #pragma unroll
             for (int k = 0; k < VEC; ++k) mx[k] = 0.f;
         }
-        sg_store<VEC>(m + row * ldm + c, mx);
+        cols_store<VEC>(m + row * ldm + c, mx);
         if (cnt) sg_store_i<VEC>(cnt + row * ldc + c, ct);
     }
 }
@@ -226,25 +185,25 @@ k_sage_max_bwd(const int32_t *__restrict__ ptr_t, const int32_t *__restrict__ ot
     constexpr int U = kEdgesSgBwd;
     int64_t row;
     int sub, L;
-    if (!sg_row<WAVE>(lg, N, row, sub, L)) return;
+    if (!seg_row<WAVE>(lg, N, row, sub, L)) return;
     const int beg = ptr_t[row], end = ptr_t[row + 1];
     for (int c = sub * VEC; c < F; c += L * VEC) {
-        const ColsSg<VEC> xj = sg_load<VEC>(x + row * ldx + c, true);
+        const Cols<VEC> xj = cols_load<VEC>(x + row * ldx + c, true);
         float acc[VEC], cmp[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = 0.f, cmp[k] = 0.f;
         for (int p = beg; p < end; p += U) {
             const int n = end - p;
             int64_t s[U];
-            ColsSg<VEC> mv[U], gv[U];
+            Cols<VEC> mv[U], gv[U];
             IntsSg<VEC> cv[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = u < n ? other_t[p + u] : row;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                mv[u] = sg_load<VEC>(m + s[u] * ldm + c, u < n);
+                mv[u] = cols_load<VEC>(m + s[u] * ldm + c, u < n);
                 cv[u] = sg_load_i<VEC>(cnt + s[u] * ldc + c, u < n);
-                gv[u] = sg_load<VEC>(gm + s[u] * ldgm + c, u < n);
+                gv[u] = cols_load<VEC>(gm + s[u] * ldgm + c, u < n);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -253,21 +212,12 @@ k_sage_max_bwd(const int32_t *__restrict__ ptr_t, const int32_t *__restrict__ ot
                     for (int k = 0; k < VEC; ++k) {
                         const bool hit = xj.a[k] == mv[u].a[k] && cv[u].a[k] > 0;
                         const float share = gv[u].a[k] / (float)(hit ? cv[u].a[k] : 1);
-                        sg_kahan(acc[k], cmp[k], hit ? share : 0.f);
+                        kahan_add(acc[k], cmp[k], hit ? share : 0.f);
                     }
                 }
         }
-        sg_store<VEC>(gx + row * ldgx + c, acc);
+        cols_store<VEC>(gx + row * ldgx + c, acc);
     }
-}
-
-static inline bool sg_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-static inline bool sg_sizes_ok(int64_t N, int64_t F) { return N < (int64_t)INT32_MAX / 4 && F < (1 << 24); }
-// log2 of the lanes per row: the power of two >= units within 4..64
-static inline int sg_log2_lanes(int64_t units) {
-    int lg = 2;
-    while (lg < 6 && (1 << lg) < units) ++lg;
-    return lg;
 }
 
 }  // namespace dc
@@ -276,12 +226,12 @@ using namespace dc;
 
 #define DC_SAGE_SHAPE(name, N, F)                                                                                  \
     DC_REQUIRE((N) >= 0 && (F) >= 1, name ": need N >= 0, F >= 1 (N=%lld F=%lld)", (long long)(N), (long long)(F)); \
-    DC_REQUIRE(sg_sizes_ok(N, F), name ": size out of range")
+    DC_REQUIRE(sizes_ok(N, F), name ": size out of range")
 
 // the four forms of a kernel: 16-byte or scalar columns, one wave per row or 64 / L rows per wave
 #define DC_SAGE_LAUNCH(kernel, v4, N, F, stream, ...)                                                              \
     do {                                                                                                           \
-        const int lg_ = sg_log2_lanes((v4) ? (F) / 4 : (F));                                                       \
+        const int lg_ = log2_lanes((v4) ? (F) / 4 : (F));                                                       \
         const int64_t rows_ = 256 >> lg_;                                                                          \
         const dim3 grid_((unsigned)(((N) + rows_ - 1) / rows_));                                                   \
         if ((v4) && lg_ == 6) DC_LAUNCH((kernel<4, true>), grid_, dim3(256), 0, stream, __VA_ARGS__, N, (int)(F), lg_); \
@@ -298,7 +248,7 @@ extern "C" int dc_sage_mean_fwd(const int32_t *ptr, const int32_t *other, const 
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && x && y, "dc_sage_mean_fwd: null pointer");
     DC_REQUIRE(y != x, "dc_sage_mean_fwd: y must not alias x");
-    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && sg_al16(x) && sg_al16(y);
+    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(y);
     DC_SAGE_LAUNCH(k_sage_mean_fwd, v4, N, F, stream, ptr, other, x, ldx, y, ldy);
     return check_launch("dc_sage_mean_fwd");
 }
@@ -311,7 +261,7 @@ extern "C" int dc_sage_mean_bwd(const int32_t *ptr_t, const int32_t *other_t, co
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr_t && other_t && ptr && gy && gx, "dc_sage_mean_bwd: null pointer");
     DC_REQUIRE(gx != gy, "dc_sage_mean_bwd: gx must not alias gy");
-    const bool v4 = F % 4 == 0 && ldgy % 4 == 0 && ldgx % 4 == 0 && sg_al16(gy) && sg_al16(gx);
+    const bool v4 = F % 4 == 0 && ldgy % 4 == 0 && ldgx % 4 == 0 && al16(gy) && al16(gx);
     DC_SAGE_LAUNCH(k_sage_mean_bwd, v4, N, F, stream, ptr_t, other_t, ptr, gy, ldgy, gx, ldgx);
     return check_launch("dc_sage_mean_bwd");
 }
@@ -325,8 +275,8 @@ extern "C" int dc_sage_max_fwd(const int32_t *ptr, const int32_t *other, const f
     DC_REQUIRE(ptr && other && x && m, "dc_sage_max_fwd: null pointer");
     DC_REQUIRE(m != x && (const void *)cnt != (const void *)x && (const void *)cnt != (const void *)m,
                "dc_sage_max_fwd: m / cnt must not alias x or each other");
-    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldm % 4 == 0 && sg_al16(x) && sg_al16(m) &&
-                    (!cnt || (ldc % 4 == 0 && sg_al16(cnt)));
+    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldm % 4 == 0 && al16(x) && al16(m) &&
+                    (!cnt || (ldc % 4 == 0 && al16(cnt)));
     DC_SAGE_LAUNCH(k_sage_max_fwd, v4, N, F, stream, ptr, other, x, ldx, m, ldm, cnt, ldc);
     return check_launch("dc_sage_max_fwd");
 }
@@ -343,7 +293,7 @@ extern "C" int dc_sage_max_bwd(const int32_t *ptr_t, const int32_t *other_t, con
     DC_REQUIRE(gx != x && gx != m && gx != gm && (const void *)gx != (const void *)cnt,
                "dc_sage_max_bwd: gx must not alias an input");
     const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldm % 4 == 0 && ldc % 4 == 0 && ldgm % 4 == 0 && ldgx % 4 == 0 &&
-                    sg_al16(x) && sg_al16(m) && sg_al16(cnt) && sg_al16(gm) && sg_al16(gx);
+                    al16(x) && al16(m) && al16(cnt) && al16(gm) && al16(gx);
     DC_SAGE_LAUNCH(k_sage_max_bwd, v4, N, F, stream, ptr_t, other_t, x, ldx, m, ldm, cnt, ldc, gm, ldgm, gx, ldgx);
     return check_launch("dc_sage_max_bwd");
 }

@@ -1,0 +1,131 @@
+// dc_segment.h -- the device and host helpers the segment kernels share (dc_gat*.hip, dc_gatv2.hip, dc_transformer.hip,
+// dc_sage.hip, dc_gine.hip, dc_gnn_epi.hip).  Internal; not for the dense / hop / attention translation units.
+//
+// These kernels promise: every sum in a fixed order, products and sums rounded separately, no float atomics - two runs
+// give the same bits.  The promise rests on the exact operation order of the helpers below, so each is defined ONCE,
+// here; a new layer's kernels include this header instead of copying.  Everything has internal linkage.
+#pragma once
+#include "dc_common.h"
+
+#pragma clang fp contract(off)
+
+namespace dc {
+
+namespace {
+
+__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
+
+// compensated running sum: (acc, cmp) += v, in the order of the calls
+__device__ __forceinline__ void kahan_add(float &acc, float &cmp, float v) {
+    const float y = v - cmp;
+    const float t = acc + y;
+    cmp = (t - acc) - y;
+    acc = t;
+}
+
+// ---- VEC columns per lane: one float, or four as a 16-byte access -----------------------------------------------------
+template <int VEC> struct Vec;
+template <> struct Vec<1> { using T = float; };
+template <> struct Vec<4> { using T = float4; };
+
+__device__ __forceinline__ float vec_zero(float) { return 0.0f; }
+__device__ __forceinline__ float4 vec_zero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
+// guarded load: zeros where !ok (p is not dereferenced then)
+template <class V>
+__device__ __forceinline__ V vec_load(const float *p, bool ok) {
+    return ok ? *reinterpret_cast<const V *>(p) : vec_zero(V{});
+}
+
+// the same as a register block whose columns can be indexed: per-column state of the kernels that sum per column
+// (the float4 is formed here, not through vec_load: the kernels of dc_sage.hip allocate other registers that way)
+template <int VEC> struct Cols { float a[VEC]; };
+template <int VEC>
+__device__ __forceinline__ Cols<VEC> cols_load(const float *p, bool ok) {
+    Cols<VEC> r;
+    if constexpr (VEC == 4) {
+        const float4 v = ok ? *reinterpret_cast<const float4 *>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+        r.a[0] = v.x, r.a[1] = v.y, r.a[2] = v.z, r.a[3] = v.w;
+    } else {
+        r.a[0] = ok ? *p : 0.f;
+    }
+    return r;
+}
+template <int VEC>
+__device__ __forceinline__ void cols_store(float *p, const float (&v)[VEC]) {
+    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *p = v[0];
+}
+
+// ---- cross-lane sums: fixed xor butterflies, widest step first; every lane of the group gets the result ---------------
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+}
+// over aligned groups of T lanes (T a power of two <= 64, a run-time value)
+__device__ __forceinline__ float group_sum(float v, int T) {
+    for (int d = T >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+}
+// over aligned sub-groups of SUB lanes (the lanes that share a destination segment; SUB is the kernel's choice)
+template <int SUB, class T>
+__device__ __forceinline__ T sub_sum(T v) {
+#pragma unroll
+    for (int d = SUB / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+}
+template <int SUB>
+__device__ __forceinline__ float sub_max(float v) {
+#pragma unroll
+    for (int d = SUB / 2; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, kWave));
+    return v;
+}
+template <int SUB>
+__device__ __forceinline__ int sub_max(int v) {
+#pragma unroll
+    for (int d = SUB / 2; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, kWave));
+    return v;
+}
+
+// the row this lane works for and its place in the row's lane group (lg = log2 L; WAVE: L = 64, row wave-uniform)
+template <bool WAVE>
+__device__ __forceinline__ bool seg_row(int lg, int64_t rows, int64_t &row, int &sub, int &L) {
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    if constexpr (WAVE) {
+        row = __builtin_amdgcn_readfirstlane((int)(lb * 4u + (threadIdx.x >> 6)));
+        sub = threadIdx.x & 63;
+        L = kWave;
+    } else {
+        L = 1 << lg;
+        row = (int64_t)lb * (256 >> lg) + (threadIdx.x >> lg);
+        sub = threadIdx.x & (L - 1);
+    }
+    return row < rows;
+}
+
+// ---- host-side checks of the entries ------------------------------------------------------------------------------------
+inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+// rows x width, and rows x heads x channels per head: what the kernels' int arithmetic holds
+inline bool sizes_ok(int64_t rows, int64_t F) { return rows < (int64_t)INT32_MAX / 4 && F < (1 << 24); }
+inline bool sizes_ok(int64_t N, int64_t H, int64_t C) {
+    return N < (int64_t)INT32_MAX / 4 && H < (1 << 16) && C < (1 << 24) && H * C < (1 << 24);
+}
+// widths the row-wise column-sum passes take: 4-column quads, a whole number of rows side by side in a workgroup
+inline bool colsum_width_ok(int64_t F) { return F >= 4 && F <= 1024 && F % 4 == 0 && 256 % (F / 4) == 0; }
+// lanes per head: the power of two >= units, at most one wave
+inline int lanes_per_head(int64_t units) {
+    int t = 1;
+    while (t < kWave && t < units) t <<= 1;
+    return t;
+}
+// log2 of the lanes per row: the power of two >= units within 4..64
+inline int log2_lanes(int64_t units) {
+    int lg = 2;
+    while (lg < 6 && (1 << lg) < units) ++lg;
+    return lg;
+}
+
+}  // namespace
+
+}  // namespace dc

@@ -8,38 +8,19 @@
 // [capacity, H], and the aggregation (dc_spmm_f32_heads_bias_act, of v) and the SDDMM (dc_sddmm_f32_heads: galpha =
 // <gm[i], v[j]>) are the ones of dc_gat_heads.hip.  The edge set is taken as given: a destination may have NO edge.
 //
-// Rules of dc_gatv2.hip: destination-sorted segments, every sum in a fixed order, products and sums rounded
-// separately, no float atomics, no host read - two runs give the same bits.  The long sums (a segment's softmax
+// Rules of the segment kernels (the order-defining helpers: see dc_segment.h): destination-sorted segments, every sum
+// in a fixed order, products and sums rounded separately, no float atomics, no host read - two runs give the same bits.
+// The long sums (a segment's softmax
 // denominator, its sum of alpha galpha, the per-column sums over a segment's edges) are compensated (Kahan).  Any
 // H >= 1, C >= 1 and in-degree, 0 included, N = 0: no width cap - what a lane cannot hold in registers it reads again
 // (forward) or works through in column chunks (backward).
-#include "dc_common.h"
+#include "dc_segment.h"
 
 #pragma clang fp contract(off)
 
 namespace dc {
 
 namespace {
-
-template <int VEC> struct VecTc;
-template <> struct VecTc<1> { using T = float; };
-template <> struct VecTc<4> { using T = float4; };
-
-// compensated running sum: (acc, cmp) += v, in the order of the calls
-__device__ __forceinline__ void tc_kahan(float &acc, float &cmp, float v) {
-    const float y = v - cmp;
-    const float t = acc + y;
-    cmp = (t - acc) - y;
-    acc = t;
-}
-
-__device__ __forceinline__ float tc_zero(float) { return 0.0f; }
-__device__ __forceinline__ float4 tc_zero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-template <class V>
-__device__ __forceinline__ V tc_load(const float *p, bool ok) {
-    return ok ? *reinterpret_cast<const V *>(p) : tc_zero(V{});
-}
 
 // acc += sum over the lane's channels of q * k, channel order
 __device__ __forceinline__ void tc_score(float &acc, float q, float k) {
@@ -53,37 +34,12 @@ __device__ __forceinline__ void tc_score(float &acc, const float4 &q, const floa
     tc_score(acc, q.w, k.w);
 }
 
-// sum over aligned groups of T lanes (T a power of two <= 64), fixed butterfly: every lane of the group gets the sum
-__device__ __forceinline__ float tc_group_sum(float v, int T) {
-    for (int d = T >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-
 // the gradient of the scaled dot product from the softmax's: ONE expression, so that the value the destination side
 // stores (gl) and the one it uses for g_q are the same bits
 __device__ __forceinline__ float tc_logit_grad(float alpha, float galpha, float dot, float scale) {
     const float d = galpha - dot;
     const float ge = alpha * d;
     return ge * scale;
-}
-
-// per-column state of the backward kernels: VEC columns of one head per lane and unit
-template <int VEC> struct ColsTc { float a[VEC]; };
-template <int VEC>
-__device__ __forceinline__ ColsTc<VEC> tc_cols(const float *p, bool ok) {
-    ColsTc<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 v = tc_load<float4>(p, ok);
-        r.a[0] = v.x, r.a[1] = v.y, r.a[2] = v.z, r.a[3] = v.w;
-    } else {
-        r.a[0] = ok ? *p : 0.f;
-    }
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ void tc_store(float *p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
 }
 
 }  // namespace
@@ -106,7 +62,7 @@ __global__ void __launch_bounds__(256)
 k_tconv_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other, const float *__restrict__ q,
                     int64_t ldq, const float *__restrict__ k, int64_t ldk, float scale, float *alpha, int64_t N, int H,
                     int C, int T) {
-    using V = typename VecTc<VEC>::T;
+    using V = typename Vec<VEC>::T;
     constexpr int U = kEdgesTc;
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
     const int64_t row = __builtin_amdgcn_readfirstlane((int)(lb * 4u + (threadIdx.x >> 6)));
@@ -124,7 +80,7 @@ k_tconv_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
 #pragma unroll
         for (int r = 0; r < kRegTc; ++r) {
             const int cu = sub + T * r;
-            qr[r] = tc_load<V>(q + row * ldq + hcol + cu * VEC, hv && cu < Cv);
+            qr[r] = vec_load<V>(q + row * ldq + hcol + cu * VEC, hv && cu < Cv);
         }
         float m = -INFINITY;
         for (int p = beg; p < end; p += U) {
@@ -143,7 +99,7 @@ k_tconv_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
                     const bool ok = hv && cu < Cv;
                     V kv[U];
 #pragma unroll
-                    for (int u = 0; u < U; ++u) kv[u] = tc_load<V>(k + s[u] * ldk + hcol + cu * VEC, ok && u < n);
+                    for (int u = 0; u < U; ++u) kv[u] = vec_load<V>(k + s[u] * ldk + hcol + cu * VEC, ok && u < n);
 #pragma unroll
                     for (int u = 0; u < U; ++u) tc_score(acc[u], qr[r], kv[u]);
                 }
@@ -151,17 +107,17 @@ k_tconv_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
             for (int r = kRegTc; r < J; ++r) {                 // heads wider than the registers hold: q read again
                 const int cu = sub + T * r;
                 const bool ok = hv && cu < Cv;
-                const V qv = tc_load<V>(q + row * ldq + hcol + cu * VEC, ok);
+                const V qv = vec_load<V>(q + row * ldq + hcol + cu * VEC, ok);
                 V kv[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) kv[u] = tc_load<V>(k + s[u] * ldk + hcol + cu * VEC, ok && u < n);
+                for (int u = 0; u < U; ++u) kv[u] = vec_load<V>(k + s[u] * ldk + hcol + cu * VEC, ok && u < n);
 #pragma unroll
                 for (int u = 0; u < U; ++u) tc_score(acc[u], qv, kv[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (u < n) {                                   // wave-uniform
-                    const float e = tc_group_sum(acc[u], T) * scale;
+                    const float e = group_sum(acc[u], T) * scale;
                     m = fmaxf(m, e);
                     if (hv && ((p + u - beg) & (T - 1)) == sub) alpha[(int64_t)(p + u) * H + h] = e;
                 }
@@ -173,9 +129,9 @@ k_tconv_softmax_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__
                 float *al = alpha + (int64_t)p * H + h;
                 const float ex = expf(*al - m);
                 *al = ex;
-                tc_kahan(sum, cmp, ex);
+                kahan_add(sum, cmp, ex);
             }
-        const float den = tc_group_sum(sum, T) + 1e-16f;
+        const float den = group_sum(sum, T) + 1e-16f;
         if (hv)
             for (int p = beg + sub; p < end; p += T) {
                 float *al = alpha + (int64_t)p * H + h;
@@ -230,8 +186,8 @@ k_tconv_dst_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
         for (int h = h_first; h <= h_last; ++h) {              // wave-uniform
             float d = 0.f, dc = 0.f;
             for (int p = beg + lane; p < end; p += kWave)
-                tc_kahan(d, dc, alpha[(int64_t)p * H + h] * galpha[(int64_t)p * H + h]);
-            d = tc_group_sum(d, kWave);
+                kahan_add(d, dc, alpha[(int64_t)p * H + h] * galpha[(int64_t)p * H + h]);
+            d = group_sum(d, kWave);
             if ((int64_t)h * C >= c0)                          // the head begins in this chunk: its gl is stored here
                 for (int p = beg + lane; p < end; p += kWave)
                     gl[(int64_t)p * H + h] = tc_logit_grad(alpha[(int64_t)p * H + h], galpha[(int64_t)p * H + h], d, scale);
@@ -246,12 +202,12 @@ k_tconv_dst_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
             for (int u = 0; u < U; ++u) s[u] = u < n ? other[p + u] : row;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                ColsTc<VEC> kv[U];
+                Cols<VEC> kv[U];
                 float g[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const bool on = ok[r] && u < n;
-                    kv[u] = tc_cols<VEC>(k + s[u] * ldk + col[r], on);
+                    kv[u] = cols_load<VEC>(k + s[u] * ldk + col[r], on);
                     const int64_t x = (int64_t)(p + u) * H + hh[r];
                     g[u] = on ? tc_logit_grad(alpha[x], galpha[x], dot[r], scale) : 0.f;
                 }
@@ -259,13 +215,13 @@ k_tconv_dst_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
                 for (int u = 0; u < U; ++u)
                     if (u < n) {                               // wave-uniform
 #pragma unroll
-                        for (int c = 0; c < VEC; ++c) tc_kahan(acc[r][c], cmp[r][c], g[u] * kv[u].a[c]);
+                        for (int c = 0; c < VEC; ++c) kahan_add(acc[r][c], cmp[r][c], g[u] * kv[u].a[c]);
                     }
             }
         }
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            if (ok[r]) tc_store<VEC>(g_q + row * ldgq + col[r], acc[r]);
+            if (ok[r]) cols_store<VEC>(g_q + row * ldgq + col[r], acc[r]);
     }
 }
 
@@ -310,13 +266,13 @@ k_tconv_src_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
             }
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                ColsTc<VEC> qv[U], gv[U];
+                Cols<VEC> qv[U], gv[U];
                 float a[U], g[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const bool on = ok[r] && u < n;
-                    qv[u] = tc_cols<VEC>(q + s[u] * ldq + col[r], on);
-                    gv[u] = tc_cols<VEC>(gm + s[u] * ldgm + col[r], on);
+                    qv[u] = cols_load<VEC>(q + s[u] * ldq + col[r], on);
+                    gv[u] = cols_load<VEC>(gm + s[u] * ldgm + col[r], on);
                     a[u] = on ? alpha[f[u] * H + hh[r]] : 0.f;
                     g[u] = on ? gl[f[u] * H + hh[r]] : 0.f;
                 }
@@ -325,8 +281,8 @@ k_tconv_src_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
                     if (u < n) {                               // wave-uniform
 #pragma unroll
                         for (int c = 0; c < VEC; ++c) {
-                            tc_kahan(ak[r][c], ck[r][c], g[u] * qv[u].a[c]);
-                            tc_kahan(av[r][c], cv[r][c], a[u] * gv[u].a[c]);
+                            kahan_add(ak[r][c], ck[r][c], g[u] * qv[u].a[c]);
+                            kahan_add(av[r][c], cv[r][c], a[u] * gv[u].a[c]);
                         }
                     }
             }
@@ -334,21 +290,10 @@ k_tconv_src_bwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ oth
 #pragma unroll
         for (int r = 0; r < R; ++r)
             if (ok[r]) {
-                tc_store<VEC>(g_k + row * ldgk + col[r], ak[r]);
-                tc_store<VEC>(g_v + row * ldgv + col[r], av[r]);
+                cols_store<VEC>(g_k + row * ldgk + col[r], ak[r]);
+                cols_store<VEC>(g_v + row * ldgv + col[r], av[r]);
             }
     }
-}
-
-static inline bool tc_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-static inline bool tc_sizes_ok(int64_t N, int64_t H, int64_t C) {
-    return N < (int64_t)INT32_MAX / 4 && H < (1 << 16) && C < (1 << 24) && H * C < (1 << 24);
-}
-// lanes per head of the forward kernel: the power of two >= units, at most one wave
-static inline int tc_lanes_per_head(int64_t units) {
-    int t = 1;
-    while (t < kWave && t < units) t <<= 1;
-    return t;
 }
 
 }  // namespace dc
@@ -358,7 +303,7 @@ using namespace dc;
 #define DC_TCONV_SHAPE(name, N, H, C)                                                                              \
     DC_REQUIRE((N) >= 0 && (H) >= 1 && (C) >= 1, name ": need N >= 0, H >= 1, C >= 1 (N=%lld H=%lld C=%lld)",     \
                (long long)(N), (long long)(H), (long long)(C));                                                    \
-    DC_REQUIRE(tc_sizes_ok(N, H, C), name ": size out of range")
+    DC_REQUIRE(sizes_ok(N, H, C), name ": size out of range")
 
 extern "C" int dc_tconv_softmax_fwd(const int32_t *ptr, const int32_t *other, const float *q, int64_t ldq,
                                     const float *k, int64_t ldk, float scale, float *alpha, int64_t N, int64_t H,
@@ -368,14 +313,14 @@ extern "C" int dc_tconv_softmax_fwd(const int32_t *ptr, const int32_t *other, co
     DC_REQUIRE(ldq >= H * C && ldk >= H * C, "dc_tconv_softmax_fwd: leading dimension smaller than H * C");
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && q && k && alpha, "dc_tconv_softmax_fwd: null pointer");
-    const bool v4 = C % 4 == 0 && ldq % 4 == 0 && ldk % 4 == 0 && tc_al16(q) && tc_al16(k);
+    const bool v4 = C % 4 == 0 && ldq % 4 == 0 && ldk % 4 == 0 && al16(q) && al16(k);
     const dim3 grid((unsigned)((N + 3) / 4));
     if (v4)
         DC_LAUNCH((k_tconv_softmax_fwd<4>), grid, dim3(256), 0, stream, ptr, other, q, ldq, k, ldk, scale, alpha, N,
-                  (int)H, (int)C, tc_lanes_per_head(C / 4));
+                  (int)H, (int)C, lanes_per_head(C / 4));
     else
         DC_LAUNCH((k_tconv_softmax_fwd<1>), grid, dim3(256), 0, stream, ptr, other, q, ldq, k, ldk, scale, alpha, N,
-                  (int)H, (int)C, tc_lanes_per_head(C));
+                  (int)H, (int)C, lanes_per_head(C));
     return check_launch("dc_tconv_softmax_fwd");
 }
 
@@ -388,7 +333,7 @@ extern "C" int dc_tconv_softmax_bwd(const int32_t *ptr, const int32_t *other, co
     if (N == 0) return DC_OK;
     DC_REQUIRE(ptr && other && alpha && galpha && k && gl && g_q, "dc_tconv_softmax_bwd: null pointer");
     DC_REQUIRE(g_q != k && gl != alpha && gl != galpha, "dc_tconv_softmax_bwd: g_q / gl must not alias an input");
-    const bool v4 = C % 4 == 0 && ldk % 4 == 0 && ldgq % 4 == 0 && tc_al16(k) && tc_al16(g_q);
+    const bool v4 = C % 4 == 0 && ldk % 4 == 0 && ldgq % 4 == 0 && al16(k) && al16(g_q);
     const dim3 grid((unsigned)((N + 3) / 4));
     if (v4)
         DC_LAUNCH((k_tconv_dst_bwd<4>), grid, dim3(256), 0, stream, ptr, other, alpha, galpha, k, ldk, scale, gl, g_q,
@@ -412,8 +357,8 @@ extern "C" int dc_tconv_source_bwd(const int32_t *ptr_t, const int32_t *other_t,
     DC_REQUIRE(ptr_t && other_t && to_fwd && alpha && gl && q && gm && g_k && g_v, "dc_tconv_source_bwd: null pointer");
     DC_REQUIRE(g_k != q && g_k != gm && g_v != q && g_v != gm && g_k != g_v,
                "dc_tconv_source_bwd: g_k / g_v must not alias q / gm or each other");
-    const bool v4 = C % 4 == 0 && ldq % 4 == 0 && ldgm % 4 == 0 && ldgk % 4 == 0 && ldgv % 4 == 0 && tc_al16(q) &&
-                    tc_al16(gm) && tc_al16(g_k) && tc_al16(g_v);
+    const bool v4 = C % 4 == 0 && ldq % 4 == 0 && ldgm % 4 == 0 && ldgk % 4 == 0 && ldgv % 4 == 0 && al16(q) &&
+                    al16(gm) && al16(g_k) && al16(g_v);
     const dim3 grid((unsigned)((N + 3) / 4));
     if (v4)
         DC_LAUNCH((k_tconv_src_bwd<4>), grid, dim3(256), 0, stream, ptr_t, other_t, to_fwd, alpha, gl, q, ldq, gm, ldgm,

@@ -149,17 +149,95 @@ def _check_inputs(x: Tensor, edge_index: Tensor, in_channels: int):
         raise RuntimeError(f"x is on {x.device} but edge_index is on {edge_index.device}")
 
 
-class TAGConv(nn.Module):
+def _check_edge_attr(edge_attr, edge_index, width: int, hint: str = "", width_note: str = "", mismatch=None) -> Tensor:
+    """The third positional argument as PyG's ``edge_attr``, checked on the host for ``GATConv`` and ``GINEConv``: a
+    tensor, resolved, float32, ``[E]`` -> ``[E, 1]`` where ``width`` is 1, 2-D of that width, one row per edge of
+    ``edge_index``.  The layers' wordings differ and are kept: ``hint`` ends the type error, ``width_note`` follows the
+    expected shape of a tensor that is not 2-D, ``mismatch(edge_attr)`` is the layer's own text for a wrong width."""
+    if not isinstance(edge_attr, Tensor):
+        raise TypeError(f"edge_attr (the third positional argument, as in PyG) must be a tensor, got "
+                        f"{type(edge_attr).__name__}{hint}")
+    edge_attr = resolve(edge_attr)
+    if edge_attr.dtype != torch.float32:
+        raise ValueError(f"edge_attr must be float32, got {edge_attr.dtype}")
+    if edge_attr.dim() == 1 and width == 1:
+        edge_attr = edge_attr.unsqueeze(-1)
+    if edge_attr.dim() != 2:
+        raise ValueError(f"edge_attr must be [E, {width}]{width_note}, got {tuple(edge_attr.shape)}")
+    if edge_attr.size(1) != width:
+        raise ValueError(mismatch(edge_attr) if mismatch is not None else
+                         f"edge_attr must be [E, {width}] (edge_dim = {width}), got {tuple(edge_attr.shape)}")
+    if isinstance(edge_index, Tensor) and edge_index.dim() == 2 and edge_attr.size(0) != edge_index.size(1):
+        raise ValueError(f"edge_attr has {edge_attr.size(0)} rows but edge_index has {edge_index.size(1)} edges")
+    return edge_attr
+
+
+class _ConvBase(nn.Module):
+    """What every conv layer shares: the adjacency it runs on.  A class states how its edge set is prepared as data
+    (``_self_loops``, ``_gcn_norm``); ``graph_flags()`` / ``graph()`` are what the loaders and the encoder call."""
+
+    _self_loops = False       # remove, then add, one self loop per node
+    _gcn_norm = False         # weights deg^-1/2 [source] deg^-1/2 [destination]
+
+    def graph_flags(self) -> dict:
+        return dict(self_loops=self._self_loops, normalize=self._gcn_norm)
+
+    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
+        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
+
+    def _init_bias(self, width: int, bias: bool) -> None:
+        """``self.bias``: a zero Parameter ``[width]``, or None."""
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(width))
+        else:
+            self.register_parameter("bias", None)
+
+
+class _ReluConv(_ConvBase):
+    """The layers that can run the ReLU behind them in their own epilogue (``relu=True``), and whose plain call returns
+    a deferred result that lets what follows decide (``DEFER_ACTIVATION``)."""
+
+    supports_fused_relu = True
+
+    @property
+    def out_width(self) -> int:
+        """Width of the output of a layer with ``heads``: side by side (``concat``) or their mean."""
+        return self.heads * self.out_channels if self.concat else self.out_channels
+
+    def _dispatch(self, x: Tensor, edge_index: Tensor, relu: bool, next_conv, width: int, empty_none: bool = False,
+                  **extra: Optional[Tensor]) -> Tensor:
+        """``self._layer(g, x, relu, *extra)`` now - or, for the plain PyG call, as a deferred result of ``width``
+        columns on the branch's stream.  ``extra``: further tensors of the call (``edge_attr=...`` or None), which must
+        be on ``x``'s device, are guarded with ``x`` and make the result want a gradient when they do.  ``empty_none``:
+        no node -> no adjacency is built and ``g`` is None."""
+        x = resolve(x)
+        _check_inputs(x, edge_index, self.in_channels)
+        for name, t in extra.items():
+            if t is not None:
+                _require_cuda(t, name)
+                if t.device != x.device:
+                    raise RuntimeError(f"x is on {x.device} but {name} is on {t.device}")
+        extra = tuple(extra.values())
+
+        def graph() -> Optional[GraphIndex]:
+            return self.graph(edge_index, x.size(0)) if x.size(0) or not empty_none else None
+        if DEFER_ACTIVATION and not relu and next_conv is None:
+            side = _branch_stream(self, x)
+            wanted = _grad_wanted(x, self) or (torch.is_grad_enabled()
+                                               and any(t is not None and t.requires_grad for t in extra))
+            return deferred(lambda act: _on_branch(side, lambda: self._layer(graph(), x, act, *extra)),
+                            x.size(0), width, x, wanted).guard(x, edge_index, *extra, *self.parameters())
+        return self._layer(graph(), x, relu, *extra)
+
+
+class TAGConv(_ReluConv):
     def __init__(self, in_channels: int, out_channels: int, K: int = 3, bias: bool = True,
                  normalize: bool = True):
         super().__init__()
         self.in_channels, self.out_channels, self.K, self.normalize = \
             in_channels, out_channels, K, normalize
         self.lins = nn.ModuleList([_Lin(in_channels, out_channels) for _ in range(K + 1)])
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(out_channels))
-        else:
-            self.register_parameter("bias", None)
+        self._init_bias(out_channels, bias)
         #: {activation fused?: (width, padded width) of the hop slab of the layer that consumed the last output}
         self._consumer_geom = {}
 
@@ -169,13 +247,7 @@ class TAGConv(nn.Module):
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
-    def graph_flags(self) -> dict:
-        return dict(self_loops=False, normalize=self.normalize)
-
-    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
-        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
-
-    supports_fused_relu = True
+    _gcn_norm = property(lambda self: self.normalize)
     #: dtype of the output when the input is bfloat16 (the bf16-storage forward path)
     bf16_out = torch.bfloat16
 
@@ -253,40 +325,24 @@ class TAGConv(nn.Module):
         return f"{self.in_channels}, {self.out_channels}, K={self.K}"
 
 
-class GCNConv(nn.Module):
+class GCNConv(_ReluConv):
+    _self_loops, _gcn_norm = True, True
+
     def __init__(self, in_channels: int, out_channels: int, bias: bool = True):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.lin = _Lin(in_channels, out_channels, initializer="glorot")
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(out_channels))
-        else:
-            self.register_parameter("bias", None)
+        self._init_bias(out_channels, bias)
 
     def reset_parameters(self):
         self.lin.reset_parameters()
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
-    def graph_flags(self) -> dict:
-        return dict(self_loops=True, normalize=True)
-
-    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
-        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
-
-    supports_fused_relu = True
-
     def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
         """``conv(x, edge_index)`` as PyG; ``relu=True`` fuses the ReLU the reference applies right after
         (``models/model.py:71,77``) - with the bias - into the aggregation launch (``ops.gcn_aggregate``)."""
-        x = resolve(x)
-        _check_inputs(x, edge_index, self.in_channels)
-        if DEFER_ACTIVATION and not relu and next_conv is None:
-            side = _branch_stream(self, x)
-            return deferred(lambda act: _on_branch(side, lambda: self._layer(self.graph(edge_index, x.size(0)), x, act)),
-                            x.size(0), self.out_channels, x, _grad_wanted(x, self)).guard(x, edge_index, *self.parameters())
-        g = self.graph(edge_index, x.size(0))
-        return self._layer(g, x, relu)
+        return self._dispatch(x, edge_index, relu, next_conv, self.out_channels)
 
     def _layer(self, g: GraphIndex, x: Tensor, relu: bool) -> Tensor:
         h = self.lin(x)
@@ -298,7 +354,9 @@ class GCNConv(nn.Module):
         return torch.relu(out) if relu else out
 
 
-class GATConv(nn.Module):
+class GATConv(_ReluConv):
+    _self_loops = True
+
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
                  negative_slope: float = 0.2, edge_dim: Optional[int] = None, fill_value="mean", bias: bool = True):
         super().__init__()
@@ -321,16 +379,8 @@ class GATConv(nn.Module):
         else:
             self.lin_edge = None
             self.register_parameter("att_edge", None)
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(self.out_width))
-        else:
-            self.register_parameter("bias", None)
+        self._init_bias(self.out_width, bias)
         self.reset_parameters()
-
-    @property
-    def out_width(self) -> int:
-        """Width of the output: the heads side by side (``concat``) or their mean."""
-        return self.heads * self.out_channels if self.concat else self.out_channels
 
     def reset_parameters(self):
         self.lin.reset_parameters()
@@ -345,15 +395,10 @@ class GATConv(nn.Module):
         if self.lin_edge is not None:
             self.lin_edge.reset_parameters()
 
-    def graph_flags(self) -> dict:
-        return dict(self_loops=True, normalize=False)
-
     def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
         # a layer with edge features lets a tagged batch take the one-launch self-loop build; without edge_dim: as before
         return graph_index(edge_index, num_nodes, segments=segments, loops_segmented=self.edge_dim is not None,
                            **self.graph_flags())
-
-    supports_fused_relu = True
 
     def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None, relu: bool = False,
                 next_conv=None) -> Tensor:
@@ -364,42 +409,12 @@ class GATConv(nn.Module):
         device of ``x``; it enters the attention logits only.  A layer with ``edge_dim`` called without it has no edge
         term."""
         x = resolve(x)
-        edge_attr = self._check_edge_attr(edge_attr, edge_index)
-        _check_inputs(x, edge_index, self.in_channels)
         if edge_attr is not None:
-            _require_cuda(edge_attr, "edge_attr")
-            if edge_attr.device != x.device:
-                raise RuntimeError(f"x is on {x.device} but edge_attr is on {edge_attr.device}")
-        if DEFER_ACTIVATION and not relu and next_conv is None:
-            side = _branch_stream(self, x)
-            wanted = _grad_wanted(x, self) or (edge_attr is not None and torch.is_grad_enabled()
-                                               and edge_attr.requires_grad)
-            return deferred(lambda act: _on_branch(side, lambda: self._layer(self.graph(edge_index, x.size(0)), x, act,
-                                                                             edge_attr)),
-                            x.size(0), self.out_width, x, wanted).guard(x, edge_index, edge_attr, *self.parameters())
-        g = self.graph(edge_index, x.size(0))
-        return self._layer(g, x, relu, edge_attr)
-
-    def _check_edge_attr(self, edge_attr, edge_index) -> Optional[Tensor]:
-        """The third positional argument as PyG's ``edge_attr`` ([E] -> [E, 1] with ``edge_dim=1``), checked on the host."""
-        if edge_attr is None:
-            return None
-        if not isinstance(edge_attr, Tensor):
-            raise TypeError(f"edge_attr (the third positional argument, as in PyG) must be a tensor, got "
-                            f"{type(edge_attr).__name__}; pass relu= / next_conv= by keyword")
-        edge_attr = resolve(edge_attr)
-        if self.edge_dim is None:
-            raise ValueError("edge_attr given to a GATConv built without edge_dim")
-        if edge_attr.dtype != torch.float32:
-            raise ValueError(f"edge_attr must be float32, got {edge_attr.dtype}")
-        if edge_attr.dim() == 1 and self.edge_dim == 1:
-            edge_attr = edge_attr.unsqueeze(-1)
-        if edge_attr.dim() != 2 or edge_attr.size(1) != self.edge_dim:
-            raise ValueError(f"edge_attr must be [E, {self.edge_dim}] (edge_dim = {self.edge_dim}), got "
-                             f"{tuple(edge_attr.shape)}")
-        if isinstance(edge_index, Tensor) and edge_index.dim() == 2 and edge_attr.size(0) != edge_index.size(1):
-            raise ValueError(f"edge_attr has {edge_attr.size(0)} rows but edge_index has {edge_index.size(1)} edges")
-        return edge_attr
+            if isinstance(edge_attr, Tensor) and self.edge_dim is None:
+                raise ValueError("edge_attr given to a GATConv built without edge_dim")
+            edge_attr = _check_edge_attr(edge_attr, edge_index, self.edge_dim, hint="; pass relu= / next_conv= by keyword",
+                                         width_note=f" (edge_dim = {self.edge_dim})")
+        return self._dispatch(x, edge_index, relu, next_conv, self.out_width, edge_attr=edge_attr)
 
     def _layer(self, g: GraphIndex, x: Tensor, relu: bool, edge_attr: Optional[Tensor] = None) -> Tensor:
         h = self.lin(x)
@@ -443,12 +458,14 @@ class GATConv(nn.Module):
                 + ("" if self.edge_dim is None else f", edge_dim={self.edge_dim}, fill_value={self.fill_value!r}"))
 
 
-class GATv2Conv(nn.Module):
+class GATv2Conv(_ReluConv):
     """PyG 2.5.2 ``GATv2Conv`` (dynamic attention): ``e_ij = att . leaky_relu(lin_l(x_j) + lin_r(x_i))`` per head, edge
     softmax over the incoming edges of i (self loops removed, then added), ``out_i = sum_j alpha_ij lin_l(x_j)``, the
     heads side by side (``concat``) or averaged, ``+ bias``.  Not supported, and absent from the signature as for
     ``GATConv``: attention dropout, ``add_self_loops=False``, ``edge_dim``, ``return_attention_weights``, bipartite
     input, bf16-stored input."""
+
+    _self_loops = True
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
                  negative_slope: float = 0.2, bias: bool = True, share_weights: bool = False):
@@ -463,16 +480,8 @@ class GATv2Conv(nn.Module):
         # as GATConv's ``lin``: the attention vector's gradient is a sum of terms that cancel - 24-bit products
         self.lin_l.six_products = self.lin_r.six_products = True
         self.att = nn.Parameter(torch.empty(1, heads, out_channels))
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(self.out_width))
-        else:
-            self.register_parameter("bias", None)
+        self._init_bias(self.out_width, bias)
         self.reset_parameters()
-
-    @property
-    def out_width(self) -> int:
-        """Width of the output: the heads side by side (``concat``) or their mean."""
-        return self.heads * self.out_channels if self.concat else self.out_channels
 
     def reset_parameters(self):
         self.lin_l.reset_parameters()
@@ -484,25 +493,10 @@ class GATv2Conv(nn.Module):
             if self.bias is not None:
                 self.bias.zero_()
 
-    def graph_flags(self) -> dict:
-        return dict(self_loops=True, normalize=False)
-
-    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
-        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
-
-    supports_fused_relu = True
-
     def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
         """``conv(x, edge_index)`` as PyG; everything behind the two linears is one autograd node on the kernels of
         dc_gatv2.hip and dc_gat_heads.hip (``ops.gatv2_conv``); ``relu=True`` also fuses the ReLU that follows."""
-        x = resolve(x)
-        _check_inputs(x, edge_index, self.in_channels)
-        if DEFER_ACTIVATION and not relu and next_conv is None:
-            side = _branch_stream(self, x)
-            return deferred(lambda act: _on_branch(side, lambda: self._layer(self.graph(edge_index, x.size(0)), x, act)),
-                            x.size(0), self.out_width, x, _grad_wanted(x, self)).guard(x, edge_index, *self.parameters())
-        g = self.graph(edge_index, x.size(0))
-        return self._layer(g, x, relu)
+        return self._dispatch(x, edge_index, relu, next_conv, self.out_width)
 
     def _layer(self, g: GraphIndex, x: Tensor, relu: bool) -> Tensor:
         xl = self.lin_l(x)
@@ -521,7 +515,7 @@ class GATv2Conv(nn.Module):
                 + (", share_weights=True" if self.share_weights else ""))
 
 
-class TransformerConv(nn.Module):
+class TransformerConv(_ReluConv):
     """PyG 2.5.2 ``TransformerConv`` (dot-product edge attention): ``e_ij = <lin_query(x_i), lin_key(x_j)> / sqrt(C)`` per
     head, edge softmax over the incoming edges of i - the edge set exactly as given: no self loop is removed or added,
     a node without in-edges aggregates 0 - ``out_i = sum_j alpha_ij lin_value(x_j)``, the heads side by side
@@ -549,40 +543,18 @@ class TransformerConv(nn.Module):
             lin.six_products = True
         self.lin_beta = _Lin(3 * self.out_width, 1) if beta else None
 
-    @property
-    def out_width(self) -> int:
-        """Width of the output: the heads side by side (``concat``) or their mean."""
-        return self.heads * self.out_channels if self.concat else self.out_channels
-
     def reset_parameters(self):
         for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip, self.lin_beta):
             if lin is not None:
                 lin.reset_parameters()
-
-    def graph_flags(self) -> dict:
-        return dict(self_loops=False, normalize=False)
-
-    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
-        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
-
-    supports_fused_relu = True
 
     def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
         """``conv(x, edge_index)`` as PyG; the attention behind the three linears is one autograd node on the kernels of
         dc_transformer.hip and dc_gat_heads.hip (``ops.transformer_conv``), the skip connection and the gate are torch
         ops.  ``relu=True``: the ReLU that follows runs in the aggregation's epilogue with ``root_weight=False`` at
         widths that pass ``ops.gat_heads_fused_ok``, else as a ``torch.relu`` behind the skip / gate."""
-        x = resolve(x)
-        _check_inputs(x, edge_index, self.in_channels)
-        if DEFER_ACTIVATION and not relu and next_conv is None:
-            side = _branch_stream(self, x)
-            return deferred(lambda act: _on_branch(side, lambda: self._layer(self._graph_of(edge_index, x), x, act)),
-                            x.size(0), self.out_width, x, _grad_wanted(x, self)).guard(x, edge_index, *self.parameters())
-        return self._layer(self._graph_of(edge_index, x), x, relu)
-
-    def _graph_of(self, edge_index: Tensor, x: Tensor) -> Optional[GraphIndex]:
         # (no node: no adjacency to build, and ``ops.transformer_conv`` launches nothing)
-        return self.graph(edge_index, x.size(0)) if x.size(0) else None
+        return self._dispatch(x, edge_index, relu, next_conv, self.out_width, empty_none=True)
 
     def _layer(self, g: Optional[GraphIndex], x: Tensor, relu: bool) -> Tensor:
         q, k, v = self.lin_query(x), self.lin_key(x), self.lin_value(x)
@@ -605,7 +577,7 @@ class TransformerConv(nn.Module):
                 + (", beta=True" if self.beta else "") + ("" if self.root_weight else ", root_weight=False"))
 
 
-class SAGEConv(nn.Module):
+class SAGEConv(_ReluConv):
     """PyG 2.5.2 ``SAGEConv`` (GraphSAGE): ``out_i = lin_l(aggr_j x_j)`` over the incoming edges of i - the edge set
     exactly as given: no self loop is removed or added, duplicates count, a node without in-edges aggregates 0 - with
     ``root_weight`` ``+ lin_r(x_i)``, with ``normalize`` followed by ``F.normalize(out, p=2, dim=-1)``.  With ``project``
@@ -635,30 +607,13 @@ class SAGEConv(nn.Module):
             if lin is not None:
                 lin.reset_parameters()
 
-    def graph_flags(self) -> dict:
-        return dict(self_loops=False, normalize=False)
-
-    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
-        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
-
-    supports_fused_relu = True
-
     def forward(self, x: Tensor, edge_index: Tensor, relu: bool = False, next_conv=None) -> Tensor:
         """``conv(x, edge_index)`` as PyG; the aggregation is one autograd node on the kernels of dc_sage.hip (the sum:
         the unweighted hop), the linears run on the dense block.  ``relu=True``: the ReLU that follows runs in
         ``lin_l``'s epilogue when nothing stands between them (``root_weight=False, normalize=False``), else as a
         ``torch.relu`` behind the layer."""
-        x = resolve(x)
-        _check_inputs(x, edge_index, self.in_channels)
-        if DEFER_ACTIVATION and not relu and next_conv is None:
-            side = _branch_stream(self, x)
-            return deferred(lambda act: _on_branch(side, lambda: self._layer(self._graph_of(edge_index, x), x, act)),
-                            x.size(0), self.out_channels, x, _grad_wanted(x, self)).guard(x, edge_index, *self.parameters())
-        return self._layer(self._graph_of(edge_index, x), x, relu)
-
-    def _graph_of(self, edge_index: Tensor, x: Tensor) -> Optional[GraphIndex]:
         # (no node: no adjacency to build, and ``ops.aggregate`` launches nothing)
-        return self.graph(edge_index, x.size(0)) if x.size(0) else None
+        return self._dispatch(x, edge_index, relu, next_conv, self.out_channels, empty_none=True)
 
     def _layer(self, g: Optional[GraphIndex], x: Tensor, relu: bool) -> Tensor:
         src = ops.dense_linear(x, self.lin.weight, self.lin.bias, relu=True) if self.lin is not None else x
@@ -686,7 +641,7 @@ def _reset_module(module: nn.Module) -> None:
             _reset_module(child)
 
 
-class _GinBase(nn.Module):
+class _GinBase(_ConvBase):
     """What ``GINConv`` and ``GINEConv`` share: the user's ``nn``, ``eps`` as a float32 ``[1]`` tensor named ``eps`` (a
     Parameter with ``train_eps``, else a buffer), the edge set taken as it is given."""
 
@@ -703,12 +658,6 @@ class _GinBase(nn.Module):
     def reset_parameters(self):
         _reset_module(self.nn)
         self.eps.data.fill_(self.initial_eps)
-
-    def graph_flags(self) -> dict:
-        return dict(self_loops=False, normalize=False)
-
-    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> GraphIndex:
-        return graph_index(edge_index, num_nodes, segments=segments, **self.graph_flags())
 
     def __repr__(self) -> str:
         return f"{self.__class__.__name__}(nn={self.nn})"
@@ -787,27 +736,16 @@ class GINEConv(_GinBase):
         return self.nn(ops.gine_aggregate(g, x, e, self.eps))
 
     def _check_edge_attr(self, edge_attr, edge_index, x: Tensor) -> Tensor:
-        """The third positional argument as PyG's ``edge_attr`` ([E] -> [E, 1] where the width is 1), checked on the host."""
+        """``_check_edge_attr`` at the width of ``edge_dim``, or of ``x`` without it, and the layer's own checks."""
         if edge_attr is None:
             raise ValueError("GINEConv needs edge_attr: conv(x, edge_index, edge_attr)")
-        if not isinstance(edge_attr, Tensor):
-            raise TypeError(f"edge_attr (the third positional argument, as in PyG) must be a tensor, got "
-                            f"{type(edge_attr).__name__}")
-        edge_attr = resolve(edge_attr)
-        if edge_attr.dtype != torch.float32:
-            raise ValueError(f"edge_attr must be float32, got {edge_attr.dtype}")
+        mismatch = None
+        if self.edge_dim is None:
+            def mismatch(e):
+                return ("Node and edge feature dimensionalities do not match. Consider setting the 'edge_dim' "
+                        f"attribute of 'GINEConv' (x has {x.size(1)} columns, edge_attr {e.size(1)})")
         width = self.edge_dim if self.edge_dim is not None else (x.size(1) if x.dim() == 2 else -1)
-        if edge_attr.dim() == 1 and width == 1:
-            edge_attr = edge_attr.unsqueeze(-1)
-        if edge_attr.dim() != 2:
-            raise ValueError(f"edge_attr must be [E, {width}], got {tuple(edge_attr.shape)}")
-        if edge_attr.size(1) != width:
-            if self.edge_dim is None:
-                raise ValueError("Node and edge feature dimensionalities do not match. Consider setting the 'edge_dim' "
-                                 f"attribute of 'GINEConv' (x has {x.size(1)} columns, edge_attr {edge_attr.size(1)})")
-            raise ValueError(f"edge_attr must be [E, {width}] (edge_dim = {width}), got {tuple(edge_attr.shape)}")
-        if isinstance(edge_index, Tensor) and edge_index.dim() == 2 and edge_attr.size(0) != edge_index.size(1):
-            raise ValueError(f"edge_attr has {edge_attr.size(0)} rows but edge_index has {edge_index.size(1)} edges")
+        edge_attr = _check_edge_attr(edge_attr, edge_index, width, mismatch=mismatch)
         if edge_attr.size(0) > 0 and edge_attr.size(1) > 1 and edge_attr.stride(1) != 1:
             raise ValueError("edge_attr: innermost dimension must be contiguous")
         return edge_attr

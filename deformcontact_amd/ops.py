@@ -1285,6 +1285,25 @@ def _mask_and_bias_grad(gy: torch.Tensor, y: Optional[torch.Tensor], bias_param,
     return (gm if gm is not None else gy), (None if (direct or not need_bias) else gb)
 
 
+class _ParamGrads:
+    """Where a backward kernel writes the gradients of ``params``: ``bufs`` are flat views of their ``.grad`` when the
+    kernel may accumulate there (``_direct_sink``; ``direct``), else fresh buffers.  ``done()`` behind the launch
+    reports the direct write, or shapes the buffers like the parameters: what ``backward`` returns for them."""
+
+    def __init__(self, params, needed, dev):
+        self.params, self.dev = params, dev
+        self.bucket = _direct_sink(params, needed)
+        self.direct = self.bucket is not None
+        self.bufs = [p.grad.view(-1) if self.direct else torch.empty(p.numel(), dtype=torch.float32, device=dev)
+                     for p in params]
+
+    def done(self):
+        if self.direct:
+            self.bucket.note_direct_write(torch.cuda.current_stream(self.dev))
+            return [None] * len(self.params)
+        return [b.view_as(p) for b, p in zip(self.bufs, self.params)]
+
+
 class _GcnAggFn(torch.autograd.Function):
     """``act(A_hat h + bias)`` of a GCNConv layer (PyG gcn_conv.py: ``propagate`` + ``out + bias``, then the encoder's
     ReLU, models/model.py:71,77) as ONE aggregation launch; backward: mask + bias gradient in one pass, then the
@@ -1351,23 +1370,14 @@ class _GatConvFn(torch.autograd.Function):
         gm, gb = _mask_and_bias_grad(gy, y, bias, need_b)
         gh, g_a_src, g_a_dst = _gat_edge_backward(g, gm, h, a_src, a_dst, alpha, slope)
         # the attention dot products' backward: gh += ga_src att_src + ga_dst att_dst, the two vector gradients
-        bucket = _direct_sink([att_src, att_dst], ctx.needs_input_grad[2:4])
-        direct = bucket is not None
-        if direct:
-            gs, gd = att_src.grad.view(-1), att_dst.grad.view(-1)
-        else:
-            gs = torch.empty(f, dtype=torch.float32, device=dev)
-            gd = torch.empty(f, dtype=torch.float32, device=dev)
+        pg = _ParamGrads([att_src, att_dst], ctx.needs_input_grad[2:4], dev)
+        gs, gd = pg.bufs
         nb = L.dc_colsum_workspace_bytes(n, f, 2)
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
         _lib.check(L.dc_gat_alpha_bwd(h.data_ptr(), f, g_a_src.data_ptr(), g_a_dst.data_ptr(), a_s.data_ptr(),
                                       a_d.data_ptr(), gh.data_ptr(), f, n, f, ws.data_ptr(), ws.numel(), gs.data_ptr(),
-                                      gd.data_ptr(), int(direct), st), "dc_gat_alpha_bwd")
-        if direct:
-            bucket.note_direct_write(torch.cuda.current_stream(dev))
-            gs = gd = None
-        else:
-            gs, gd = gs.view_as(att_src), gd.view_as(att_dst)
+                                      gd.data_ptr(), int(pg.direct), st), "dc_gat_alpha_bwd")
+        gs, gd = pg.done()
         return None, gh, gs, gd, gb, None, None
 
 
@@ -1454,6 +1464,17 @@ def _heads_spread(gm, nh: int, c: int) -> torch.Tensor:
     _lib.check(_lib.lib().dc_spread_heads_f32(gm.data_ptr(), _rowmajor(gm, "gm"), out.data_ptr(), nh * c, n, nh, c,
                                               current_stream_ptr(dev)), "dc_spread_heads_f32")
     return out
+
+
+def _heads_out_grad(ctx, gy, y, bias):
+    """How the multi-head backward passes open: ``gy`` in a layout the kernels take, the ReLU mask and the bias
+    gradient in one pass (``bias`` is input 4 of every one of them), and - the heads averaged - the gradient spread to
+    the heads.  -> (gm [N, H*C], gb)."""
+    gy = _grad_layout(gy, 0)
+    gm, gb = _mask_and_bias_grad(gy, y, bias, bias is not None and ctx.needs_input_grad[4])
+    if ctx.mean:
+        gm = _heads_spread(gm, ctx.nh, ctx.c)
+    return gm, gb
 
 
 def _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh: int, c: int, gs, gd, accumulate: bool) -> None:
@@ -1552,27 +1573,12 @@ class _GatHeadsConvFn(torch.autograd.Function):
         h, a_src, a_dst, alpha, a_s, a_d, y = ctx.saved_tensors
         g, slope, nh, c = ctx.g, ctx.slope, ctx.nh, ctx.c
         att_src, att_dst, bias = ctx.params
-        gy = _grad_layout(gy, 0)
-        dev = h.device
-        need_b = bias is not None and ctx.needs_input_grad[4]
-        gm, gb = _mask_and_bias_grad(gy, y, bias, need_b)
-        if ctx.mean:
-            gm = _heads_spread(gm, nh, c)
+        gm, gb = _heads_out_grad(ctx, gy, y, bias)
         gh, g_a_src, g_a_dst, _ = _gat_heads_edge_backward(g, gm, h, a_src, a_dst, alpha, slope, nh, c)
         # the attention dot products' backward: gh += ga_src att_src + ga_dst att_dst per head, the two [H, C] gradients
-        bucket = _direct_sink([att_src, att_dst], ctx.needs_input_grad[2:4])
-        direct = bucket is not None
-        if direct:
-            gs, gd = att_src.grad.view(-1), att_dst.grad.view(-1)
-        else:
-            gs = torch.empty(nh * c, dtype=torch.float32, device=dev)
-            gd = torch.empty(nh * c, dtype=torch.float32, device=dev)
-        _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh, c, gs, gd, direct)
-        if direct:
-            bucket.note_direct_write(torch.cuda.current_stream(dev))
-            gs = gd = None
-        else:
-            gs, gd = gs.view_as(att_src), gd.view_as(att_dst)
+        pg = _ParamGrads([att_src, att_dst], ctx.needs_input_grad[2:4], h.device)
+        _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh, c, *pg.bufs, pg.direct)
+        gs, gd = pg.done()
         return None, gh, gs, gd, gb, None, None, None, None
 
 
@@ -1654,23 +1660,12 @@ class _Gatv2ConvFn(torch.autograd.Function):
         xl, xr, alpha, a, y = ctx.saved_tensors
         g, slope, nh, c = ctx.g, ctx.slope, ctx.nh, ctx.c
         att, bias = ctx.params
-        gy = _grad_layout(gy, 0)
-        dev = xl.device
-        need_b = bias is not None and ctx.needs_input_grad[4]
-        gm, gb = _mask_and_bias_grad(gy, y, bias, need_b)
-        if ctx.mean:
-            gm = _heads_spread(gm, nh, c)
+        gm, gb = _heads_out_grad(ctx, gy, y, bias)
         galpha = _heads_sddmm(g, gm, xl, nh, c)
-        bucket = _direct_sink([att], ctx.needs_input_grad[3:4])
-        direct = bucket is not None
-        g_att = att.grad.view(-1) if direct else torch.empty(nh * c, dtype=torch.float32, device=dev)
-        ge, g_xr = _gatv2_softmax_bwd(g, alpha, galpha, xl, xr, a, slope, nh, c, g_att, direct)
+        pg = _ParamGrads([att], ctx.needs_input_grad[3:4], xl.device)
+        ge, g_xr = _gatv2_softmax_bwd(g, alpha, galpha, xl, xr, a, slope, nh, c, pg.bufs[0], pg.direct)
         g_xl = _gatv2_source_bwd(g, alpha, ge, gm, xl, xr, a, slope, nh, c)
-        if direct:
-            bucket.note_direct_write(torch.cuda.current_stream(dev))
-            g_att = None
-        else:
-            g_att = g_att.view_as(att)
+        (g_att,) = pg.done()
         return None, g_xl, g_xr, g_att, gb, None, None, None, None
 
 
@@ -1848,28 +1843,13 @@ class _GatHeadsEdgeConvFn(torch.autograd.Function):
         h, a_src, a_dst, alpha, a_s, a_d, y, a_edge, loop_attr, edge_attr, m = ctx.saved_tensors
         g, slope, nh, c = ctx.g, ctx.slope, ctx.nh, ctx.c
         att_src, att_dst, bias = ctx.params
-        gy = _grad_layout(gy, 0)
-        dev = h.device
-        need_b = bias is not None and ctx.needs_input_grad[4]
-        gm, gb = _mask_and_bias_grad(gy, y, bias, need_b)
-        if ctx.mean:
-            gm = _heads_spread(gm, nh, c)
+        gm, gb = _heads_out_grad(ctx, gy, y, bias)
         gh, g_a_src, g_a_dst, ge = _gat_heads_edge_backward(g, gm, h, a_src, a_dst, alpha, slope, nh, c, a_edge)
         g_attr, g_m = _edge_term_bwd(g, ge, edge_attr, loop_attr, m, ctx.fill_mean, h.size(0), nh,
                                      ctx.needs_input_grad[9], ctx.needs_input_grad[10])
-        bucket = _direct_sink([att_src, att_dst], ctx.needs_input_grad[2:4])
-        direct = bucket is not None
-        if direct:
-            gs, gd = att_src.grad.view(-1), att_dst.grad.view(-1)
-        else:
-            gs = torch.empty(nh * c, dtype=torch.float32, device=dev)
-            gd = torch.empty(nh * c, dtype=torch.float32, device=dev)
-        _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh, c, gs, gd, direct)
-        if direct:
-            bucket.note_direct_write(torch.cuda.current_stream(dev))
-            gs = gd = None
-        else:
-            gs, gd = gs.view_as(att_src), gd.view_as(att_dst)
+        pg = _ParamGrads([att_src, att_dst], ctx.needs_input_grad[2:4], h.device)
+        _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh, c, *pg.bufs, pg.direct)
+        gs, gd = pg.done()
         return None, gh, gs, gd, gb, None, None, None, None, g_attr, g_m, None, None
 
 
@@ -2005,10 +1985,7 @@ class _TransformerAggFn(torch.autograd.Function):
             z = gy.new_zeros((0, nh * c))
             return None, z, z, z, (gy.new_zeros(gy.size(1)) if need_b else None), None, None, None
         q, k, v, alpha, y = ctx.saved_tensors
-        gy = _grad_layout(gy, 0)
-        gm, gb = _mask_and_bias_grad(gy, y, bias, need_b)
-        if ctx.mean:
-            gm = _heads_spread(gm, nh, c)
+        gm, gb = _heads_out_grad(ctx, gy, y, bias)
         galpha = _heads_sddmm(g, gm, v, nh, c)
         gl, g_q = _tconv_softmax_bwd(g, alpha, galpha, k, nh, c)
         g_k, g_v = _tconv_source_bwd(g, alpha, gl, q, gm, nh, c)

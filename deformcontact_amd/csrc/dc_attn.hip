@@ -101,7 +101,6 @@ k_attn_ds_rows(const float *__restrict__ p, float *__restrict__ dp, int64_t ld, 
 // floats a 256-thread workgroup can hold the whole row in registers (NV float4 per thread): ONE global read per
 // input row, one write.  Same formulas; the partition of a row over the threads differs from the strided
 // kernels, so sums agree to rounding, not bit for bit.
-using af32x4 = __attribute__((ext_vector_type(4))) float;
 
 template <int NV>
 __global__ void __launch_bounds__(256)
@@ -109,7 +108,7 @@ k_attn_softmax_rows_reg(float *__restrict__ s, int64_t ld, int64_t n64, int64_t 
     __shared__ float red[4];
     float *row = s + (int64_t)blockIdx.x * ld;
     const int n = (int)n64, npad = (int)npad64;
-    af32x4 v[NV];
+    f32x4 v[NV];
     // columns >= n (key padding) are loaded as -inf: they drop out of the maximum, add exp(-inf) = 0 to the
     // sum and come out of the last pass as exactly 0 - no per-element tests after the load
     float m = -INFINITY;
@@ -117,14 +116,14 @@ k_attn_softmax_rows_reg(float *__restrict__ s, int64_t ld, int64_t n64, int64_t 
     for (int j = 0; j < NV; ++j) {
         const int i = (j * 256 + (int)threadIdx.x) * 4;
         if (i < npad) {
-            v[j] = *reinterpret_cast<const af32x4 *>(row + i);
+            v[j] = *reinterpret_cast<const f32x4 *>(row + i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 v[j][e] = i + e < n ? v[j][e] : -INFINITY;
                 m = fmaxf(m, v[j][e]);
             }
         } else {
-            v[j] = af32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            v[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         }
     }
     m = block_reduce_max(m, red);
@@ -139,10 +138,10 @@ k_attn_softmax_rows_reg(float *__restrict__ s, int64_t ld, int64_t n64, int64_t 
     for (int j = 0; j < NV; ++j) {
         const int i = (j * 256 + (int)threadIdx.x) * 4;
         if (i < npad) {
-            af32x4 o;
+            f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = expf(v[j][e] - l);
-            *reinterpret_cast<af32x4 *>(row + i) = o;
+            *reinterpret_cast<f32x4 *>(row + i) = o;
         }
     }
     if (threadIdx.x == 0) lse[blockIdx.x] = l;
@@ -157,14 +156,14 @@ k_attn_ds_rows_reg(const float *__restrict__ p, float *__restrict__ dp, int64_t 
     __shared__ float red[4];
     const float *pr = p + (int64_t)blockIdx.x * ld;
     float *dr = dp + (int64_t)blockIdx.x * ld;
-    af32x4 vp[NV], vd[NV];
+    f32x4 vp[NV], vd[NV];
     float acc = 0.f, sp = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const int64_t i = ((int64_t)j * 256 + threadIdx.x) * 4;
         if (i < npad) {
-            vp[j] = *reinterpret_cast<const af32x4 *>(pr + i);
-            vd[j] = *reinterpret_cast<const af32x4 *>(dr + i);
+            vp[j] = *reinterpret_cast<const f32x4 *>(pr + i);
+            vd[j] = *reinterpret_cast<const f32x4 *>(dr + i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 acc += vp[j][e] * vd[j][e];
@@ -180,13 +179,13 @@ k_attn_ds_rows_reg(const float *__restrict__ p, float *__restrict__ dp, int64_t 
     for (int j = 0; j < NV; ++j) {
         const int64_t i = ((int64_t)j * 256 + threadIdx.x) * 4;
         if (i < npad) {
-            af32x4 o;
+            f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 o[e] = vp[j][e] * (vd[j][e] - d);
                 m = fmaxf(m, fabsf(o[e]));
             }
-            *reinterpret_cast<af32x4 *>(dr + i) = o;
+            *reinterpret_cast<f32x4 *>(dr + i) = o;
         }
     }
     m = block_reduce_max(m, red);

@@ -46,9 +46,7 @@
 
 namespace dc {
 
-using fl_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using fl_f32x4 = __attribute__((ext_vector_type(4))) float;
-using fl_u32x2 = __attribute__((ext_vector_type(2))) unsigned;
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 
 constexpr int kFlD = DC_ATTN_FLASH_D;          // d = dv
 constexpr int kFlQ = 128;                      // queries per workgroup (4 waves x 32)
@@ -74,11 +72,6 @@ struct FlashParams {
     float *lse;            // [ns]
 };
 
-__device__ __forceinline__ int fl_vswz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 1); }   // as hw_swz
-
-#define DC_FL_GPTR(p) ((const void __attribute__((address_space(1))) *)(p))
-#define DC_FL_LPTR(p) ((void __attribute__((address_space(3))) *)(p))
-
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_attn_flash_fwd(FlashParams p) {
     __shared__ __attribute__((aligned(16))) char smem[kFlSmem];
@@ -92,13 +85,13 @@ k_attn_flash_fwd(FlashParams p) {
     // ---- this lane's query as B-operand fragments: k = 16 ks + 8 fh + 0..7, scaled and split as dc_dense_h2w does
     const float qm = p.qmax[qrow];
     const float sq = h2_scale(qm), uq = h2_unscale(qm);
-    fl_f16x8 qh[16], ql[16];
+    f16x8 qh[16], ql[16];
     {
         const float *qp = p.q + qrow * p.ldq + 8 * fh;
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) {
-            const fl_f32x4 a = *reinterpret_cast<const fl_f32x4 *>(qp + 16 * ks) * sq;
-            const fl_f32x4 b = *reinterpret_cast<const fl_f32x4 *>(qp + 16 * ks + 4) * sq;
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(qp + 16 * ks) * sq;
+            const f32x4 b = *reinterpret_cast<const f32x4 *>(qp + 16 * ks + 4) * sq;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const _Float16 ha = (_Float16)a[i], hb = (_Float16)b[i];
@@ -114,27 +107,27 @@ k_attn_flash_fwd(FlashParams p) {
     // ---- LDS-DMA staging.  An instruction moves 64 x 16 bytes into 1 KB of consecutive LDS: lane l fills slot l.
     // K tile (32 rows of 1 KB, piece pc of row r in slot pc ^ (r & 15)): instruction (jj, hi) of wave w fills row
     // r = 4 w + jj + 16 hi, whose swizzle only depends on 4 w + jj - four lane offsets.  V^T tile (256 rows of 128 B,
-    // piece q of row r in slot q ^ vswz(r)): instruction I = 8 w + j fills rows 8 I .. 8 I + 7 (lane l: row 8 I + (l >> 3),
-    // slot l & 7); vswz only depends on the low 4 row bits = 8 (I & 1) + (l >> 3) - two lane offsets.
+    // piece q of row r in slot q ^ lds_row_swz(r)): instruction I = 8 w + j fills rows 8 I .. 8 I + 7 (lane l: row 8 I + (l >> 3),
+    // slot l & 7); lds_row_swz only depends on the low 4 row bits = 8 (I & 1) + (l >> 3) - two lane offsets.
     const int nt = (int)((p.nr + kFlT - 1) / kFlT);
     unsigned kso[4], vso[2];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) kso[jj] = (unsigned)((4 * wid + jj) * kFlKRow + 16 * (lane ^ (4 * wid + jj)));
 #pragma unroll
     for (int e = 0; e < 2; ++e)
-        vso[e] = (unsigned)((lane >> 3) * (p.nrp * 4) + 16 * ((lane & 7) ^ fl_vswz(8 * e + (lane >> 3))));
+        vso[e] = (unsigned)((lane >> 3) * (p.nrp * 4) + 16 * ((lane & 7) ^ lds_row_swz(8 * e + (lane >> 3))));
     const int64_t v8rows = 8 * p.nrp * 4;               // bytes between the row groups of consecutive V^T instructions
     auto dma_k = [&](int t, int slot, int c) {           // instruction c (0..7) of this wave for K tile t
         const int jj = c & 3, hi = c >> 2;
         const char *src = p.kimg + (int64_t)t * kFlKSz + hi * 16 * kFlKRow;
         char *dst = sK + slot * kFlKSz + (4 * wid + jj + 16 * hi) * kFlKRow;
-        __builtin_amdgcn_global_load_lds(DC_FL_GPTR(src + kso[jj]), DC_FL_LPTR(dst), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + kso[jj]), DC_DMA_DST(dst), 16, 0, 0);
     };
     auto dma_v = [&](int t, int slot, int c) {           // instruction c (0..7) of this wave for V^T tile t
         const int I = 8 * wid + c;
         const char *src = p.vtimg + (int64_t)t * kFlVRow + I * v8rows;
         char *dst = sV + slot * kFlVSz + I * 1024;
-        __builtin_amdgcn_global_load_lds(DC_FL_GPTR(src + vso[c & 1]), DC_FL_LPTR(dst), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + vso[c & 1]), DC_DMA_DST(dst), 16, 0, 0);
     };
 
     // fragment read offsets: the swizzle only touches the low 4 bits of a piece index, so 8 (K: k-step & 3, plane) and
@@ -144,7 +137,7 @@ k_attn_flash_fwd(FlashParams p) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) kfo[c] = fr * kFlKRow + 16 * ((4 * (c >> 1) + 2 * (c & 1) + fh) ^ (fr & 15));
 #pragma unroll
-    for (int c = 0; c < 4; ++c) vfo[c] = fr * kFlVRow + 16 * ((4 * (c >> 1) + 2 * (c & 1) + fh) ^ fl_vswz(fr));
+    for (int c = 0; c < 4; ++c) vfo[c] = fr * kFlVRow + 16 * ((4 * (c >> 1) + 2 * (c & 1) + fh) ^ lds_row_swz(fr));
     f32x16 oacc[8];
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt)
@@ -178,7 +171,7 @@ k_attn_flash_fwd(FlashParams p) {
         }
     };
     load_uk(0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0)
+    DC_WAITVM(0);
     __builtin_amdgcn_s_barrier();
     int kslot = 0;                                       // t % 3
     for (int t = 0; t < nt; ++t) {
@@ -198,11 +191,11 @@ k_attn_flash_fwd(FlashParams p) {
             // k-step.  Ring of four fragment sets, reads three k-steps ahead, counted waits (LDS returns in order).
             unsigned ka[8];
             {
-                const unsigned kbase = (unsigned)(uintptr_t)DC_FL_LPTR(sK + kslot * kFlKSz);
+                const unsigned kbase = lds_addr(sK + kslot * kFlKSz);
 #pragma unroll
                 for (int c = 0; c < 8; ++c) ka[c] = kbase + (unsigned)kfo[c];
             }
-            fl_f16x8 kh[4], kl[4];
+            f16x8 kh[4], kl[4];
             auto kfrags = [&](int ks) {
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(kh[ks & 3]) : "v"(ka[2 * (ks & 3)]), "i"((ks >> 2) * 256));
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(kl[ks & 3]) : "v"(ka[2 * (ks & 3) + 1]), "i"((ks >> 2) * 256));
@@ -252,7 +245,7 @@ k_attn_flash_fwd(FlashParams p) {
             for (int i = 0; i < 16; ++i)
                 if (kbase + (i & 3) + 8 * (i >> 2) >= p.nr) s[i] = -INFINITY;
         }
-        fl_f16x8 ph[2], pl[2];
+        f16x8 ph[2], pl[2];
         {
             float tm = s[0];
 #pragma unroll
@@ -284,11 +277,11 @@ k_attn_flash_fwd(FlashParams p) {
         {
             unsigned va[4];
             {
-                const unsigned vbase = (unsigned)(uintptr_t)DC_FL_LPTR(sV + vbuf * kFlVSz);
+                const unsigned vbase = lds_addr(sV + vbuf * kFlVSz);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) va[c] = vbase + (unsigned)vfo[c];
             }
-            fl_f16x8 vh[4], vl[4];                       // ring of four fragment sets, reads three steps ahead
+            f16x8 vh[4], vl[4];                       // ring of four fragment sets, reads three steps ahead
             auto vfrags = [&](int c) {                   // c = 2 mt + m
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(vh[c & 3]) : "v"(va[2 * (c & 1)]), "i"((c >> 1) * 32 * kFlVRow));
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(vl[c & 3]) : "v"(va[2 * (c & 1) + 1]), "i"((c >> 1) * 32 * kFlVRow));
@@ -326,8 +319,8 @@ k_attn_flash_fwd(FlashParams p) {
         }
         if (t + 1 < nt) load_uk((int64_t)(t + 1) * kFlT);   // the next tile's key scales (arrive under the barrier)
         // V^T(t+1) (and K(t+1), older) must have landed; the 8 instructions of K(t+2) may stay in flight
-        if (more_k) __builtin_amdgcn_s_waitcnt(0x0F70 | 8);
-        else __builtin_amdgcn_s_waitcnt(0x0F70);
+        if (more_k) DC_WAITVM(8);
+        else DC_WAITVM(0);
         __builtin_amdgcn_s_barrier();
         kslot = kslot == 2 ? 0 : kslot + 1;
 
@@ -342,20 +335,20 @@ k_attn_flash_fwd(FlashParams p) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int dv = 32 * mt + 8 * g + 4 * fh;
-            const fl_f32x4 uv = {h2_unscale(p.vtmax[dv]), h2_unscale(p.vtmax[dv + 1]), h2_unscale(p.vtmax[dv + 2]),
+            const f32x4 uv = {h2_unscale(p.vtmax[dv]), h2_unscale(p.vtmax[dv + 1]), h2_unscale(p.vtmax[dv + 2]),
                                  h2_unscale(p.vtmax[dv + 3])};
-            fl_f32x4 v;
+            f32x4 v;
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = (oacc[mt][4 * g + i] * uv[i]) * inv_l;
-            *reinterpret_cast<fl_f32x4 *>(so + fr * kFlORow + dv) = v;
+            *reinterpret_cast<f32x4 *>(so + fr * kFlORow + dv) = v;
         }
     if (fh == 0 && q0 + fr < p.ns) p.lse[q0 + fr] = m_run + logf(l_run);
     __syncthreads();
 #pragma unroll 4
     for (int r = 0; r < 32; ++r) {
         if (q0 + r < p.ns)
-            *reinterpret_cast<fl_f32x4 *>(p.o + (q0 + r) * p.ldo + 4 * lane) =
-                *reinterpret_cast<const fl_f32x4 *>(so + r * kFlORow + 4 * lane);
+            *reinterpret_cast<f32x4 *>(p.o + (q0 + r) * p.ldo + 4 * lane) =
+                *reinterpret_cast<const f32x4 *>(so + r * kFlORow + 4 * lane);
     }
 }
 
@@ -412,16 +405,16 @@ k_attn_flash_ds(FlashDsParams p) {
     // ---- q and dO rows of this lane's query as B-operand fragments, pinned to the accumulation registers
     const float uq = h2_unscale(p.qmax[qrow]), ugo = h2_unscale(p.gomax[qrow]);
     const float lse_q = p.lse[qrow];
-    fl_f16x8 qh[16], ql[16], gh[16], gl[16];
+    f16x8 qh[16], ql[16], gh[16], gl[16];
     {
         const float sq = h2_scale(p.qmax[qrow]), sg = h2_scale(p.gomax[qrow]);
         const float *qp = p.q + qrow * p.ldq + 8 * fh, *gp = p.go + qrow * p.ldgo + 8 * fh;
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) {
-            const fl_f32x4 a = *reinterpret_cast<const fl_f32x4 *>(qp + 16 * ks) * sq;
-            const fl_f32x4 b = *reinterpret_cast<const fl_f32x4 *>(qp + 16 * ks + 4) * sq;
-            const fl_f32x4 c = *reinterpret_cast<const fl_f32x4 *>(gp + 16 * ks) * sg;
-            const fl_f32x4 e = *reinterpret_cast<const fl_f32x4 *>(gp + 16 * ks + 4) * sg;
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(qp + 16 * ks) * sq;
+            const f32x4 b = *reinterpret_cast<const f32x4 *>(qp + 16 * ks + 4) * sq;
+            const f32x4 c = *reinterpret_cast<const f32x4 *>(gp + 16 * ks) * sg;
+            const f32x4 e = *reinterpret_cast<const f32x4 *>(gp + 16 * ks + 4) * sg;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const _Float16 ha = (_Float16)a[i], hb = (_Float16)b[i], hc = (_Float16)c[i], he = (_Float16)e[i];
@@ -442,7 +435,7 @@ k_attn_flash_ds(FlashDsParams p) {
         const int jj = c & 3, hi = c >> 2;
         const char *src = img + (int64_t)t * kFlKSz + hi * 16 * kFlKRow;
         char *dst = buf + slot * kFlKSz + (4 * wid + jj + 16 * hi) * kFlKRow;
-        __builtin_amdgcn_global_load_lds(DC_FL_GPTR(src + kso[jj]), DC_FL_LPTR(dst), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + kso[jj]), DC_DMA_DST(dst), 16, 0, 0);
     };
     int kfo[8];
 #pragma unroll
@@ -458,12 +451,12 @@ k_attn_flash_ds(FlashDsParams p) {
     };
     // one product chain: acc = tile rows (A, from LDS) x resident fragments (B, accumulation registers); ring of four
     // fragment sets, reads three k-steps ahead, counted waits; hook(ks) issues this step's DMA instruction
-    auto chain = [&](f32x16 &acc, const char *tile, fl_f16x8 (&bh)[16], fl_f16x8 (&bl)[16], auto hook) {
+    auto chain = [&](f32x16 &acc, const char *tile, f16x8 (&bh)[16], f16x8 (&bl)[16], auto hook) {
         unsigned ka[8];
-        const unsigned base = (unsigned)(uintptr_t)DC_FL_LPTR(tile);
+        const unsigned base = lds_addr(tile);
 #pragma unroll
         for (int c = 0; c < 8; ++c) ka[c] = base + (unsigned)kfo[c];
-        fl_f16x8 ah[4], al[4];
+        f16x8 ah[4], al[4];
         auto frags = [&](int ks) {
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ah[ks & 3]) : "v"(ka[2 * (ks & 3)]), "i"((ks >> 2) * 256));
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(al[ks & 3]) : "v"(ka[2 * (ks & 3) + 1]), "i"((ks >> 2) * 256));
@@ -502,7 +495,7 @@ k_attn_flash_ds(FlashDsParams p) {
         for (int c = 0; c < 8; ++c) dma_rows(p.vimg, sV, 0, 0, c);
         f32x16 uk0, uk1;
         load_us(kunsc, 0, uk0, uk1);
-        __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0)
+        DC_WAITVM(0);
         __builtin_amdgcn_s_barrier();
         for (int t = 0; t < nt; ++t) {
             const int buf = t & 1;
@@ -556,20 +549,20 @@ k_attn_flash_ds(FlashDsParams p) {
                     float *mat = (mtx ? p.dsmat : p.pmat) + (q0 + (lane >> 3)) * p.ldp + col0;
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
-                        *reinterpret_cast<fl_f32x4 *>(sT + fr * kDsTRow + 8 * g + 4 * fh) =
-                            fl_f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
+                        *reinterpret_cast<f32x4 *>(sT + fr * kDsTRow + 8 * g + 4 * fh) =
+                            f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
                     asm volatile("" ::: "memory");      // (LDS operations of one wave complete in order)
-                    fl_f32x4 o[4];
+                    f32x4 o[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        o[j] = *reinterpret_cast<const fl_f32x4 *>(sT + (8 * j + (lane >> 3)) * kDsTRow + 4 * (lane & 7));
+                        o[j] = *reinterpret_cast<const f32x4 *>(sT + (8 * j + (lane >> 3)) * kDsTRow + 4 * (lane & 7));
                     if (full) {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) *reinterpret_cast<fl_f32x4 *>(mat + 8 * j * p.ldp) = o[j];
+                        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4 *>(mat + 8 * j * p.ldp) = o[j];
                     } else {
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
-                            if (q0 + 8 * j + (lane >> 3) < p.ns) *reinterpret_cast<fl_f32x4 *>(mat + 8 * j * p.ldp) = o[j];
+                            if (q0 + 8 * j + (lane >> 3) < p.ns) *reinterpret_cast<f32x4 *>(mat + 8 * j * p.ldp) = o[j];
                     }
                     asm volatile("" ::: "memory");
                 }
@@ -579,8 +572,8 @@ k_attn_flash_ds(FlashDsParams p) {
             // after them may stay in flight (VMEM operations retire in order) - but only a wave whose 32 queries all
             // exist issues exactly 8: in a ragged last tile a predicated store with no live lane is branched around,
             // and vmcnt(8) would then leave DMA pieces of V(t+1) / K(t+1) in flight past the barrier
-            if (sweep && full_tile) __builtin_amdgcn_s_waitcnt(0x0F70 | 8);
-            else __builtin_amdgcn_s_waitcnt(0x0F70);
+            if (sweep && full_tile) DC_WAITVM(8);
+            else DC_WAITVM(0);
             __builtin_amdgcn_s_barrier();
         }
         if (!sweep) {
@@ -600,11 +593,11 @@ k_attn_flash_ds(FlashDsParams p) {
 
 // the V^T image with the 4-key chunks (8 bytes) of every plane of every 64-byte record in the order (c0, c2, c1, c3)
 __global__ void __launch_bounds__(256)
-k_attn_flash_vt_image(fl_u32x2 *img, int64_t nchunks) {
+k_attn_flash_vt_image(u32x2 *img, int64_t nchunks) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // one thread per 32-byte plane
     if (4 * i >= nchunks) return;
-    fl_u32x2 *c = img + 4 * i;
-    const fl_u32x2 c1 = c[1], c2 = c[2];
+    u32x2 *c = img + 4 * i;
+    const u32x2 c1 = c[1], c2 = c[2];
     c[1] = c2, c[2] = c1;
 }
 
@@ -626,7 +619,7 @@ extern "C" int dc_attn_flash_prep(void *vt_image, int64_t dv, int64_t nr_padded,
         DC_REQUIRE(vt_image && ((uintptr_t)vt_image & 15) == 0, "dc_attn_flash_prep: null or misaligned image");
         const int64_t nthreads = nchunks / 4;
         DC_LAUNCH(k_attn_flash_vt_image, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0,
-                           (hipStream_t)stream, (fl_u32x2 *)vt_image, nchunks);
+                           (hipStream_t)stream, (u32x2 *)vt_image, nchunks);
     }
     if (nr_padded > 0) {
         DC_REQUIRE(k_rowmax && k_unscale, "dc_attn_flash_prep: null key maxima / output");

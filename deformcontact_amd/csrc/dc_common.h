@@ -21,6 +21,8 @@ inline void trace_kernel(const char *name) {
     if (__builtin_expect(g_trace_on, 0)) trace_kernel_slow(name);
 }
 
+inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
 inline int check_launch(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -48,6 +50,31 @@ __device__ __forceinline__ float inv_sqrt_count(int d) {
     return d > 0 ? 1.0f / sqrtf((float)d) : 0.0f;
 }
 
+// ---- primitives with users outside the dense family (dc_spmm.hip, dc_hopchain.hip, dc_attn.hip); the dense
+// kernels' own are in dc_dense.h ----
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+
+// an LDS object's 32-bit byte address (for offsets folded by hand)
+__device__ __forceinline__ unsigned lds_addr(const void *p) {
+    return (unsigned)(uintptr_t)(const void __attribute__((address_space(3))) *)p;
+}
+
+// this wave's LDS operations have completed (reads returned, writes landed), then the workgroup meets.  NOT
+// __syncthreads(): its fence also waits for vmcnt(0), i.e. for global loads issued ahead on purpose and for stores
+// that may keep draining
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// fp32 -> bf16 bits, round to nearest even, NaN kept quiet
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // quiet NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
 }  // namespace dc
 
 // every kernel launch of the library: the kernel expression as written (template arguments included) goes to the
@@ -57,6 +84,15 @@ __device__ __forceinline__ float inv_sqrt_count(int d) {
         dc::trace_kernel(#kernel);                 \
         hipLaunchKernelGGL(kernel, __VA_ARGS__);   \
     } while (0)
+
+// the global source and the LDS destination of the LDS-DMA builtins (__builtin_amdgcn_global_load_lds,
+// __builtin_amdgcn_raw_ptr_buffer_load_lds).  Macros, not functions: called through a __device__ function from a
+// kernel template, the host pass silently dropped the template's instantiations (k_fwd_h2: undefined launch stubs)
+#define DC_DMA_SRC(p) ((const void __attribute__((address_space(1))) *)(p))
+#define DC_DMA_DST(p) ((void __attribute__((address_space(3))) *)(p))
+
+// s_waitcnt vmcnt(n) only: the other counters stay as they are
+#define DC_WAITVM(n) __builtin_amdgcn_s_waitcnt(0x0F70 | ((n) & 15) | (((n) >> 4) << 14))
 
 #define DC_REQUIRE(cond, ...)            \
     do {                                 \

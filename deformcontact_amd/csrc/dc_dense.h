@@ -1,5 +1,7 @@
 // dc_dense.h -- shared pieces of the dense-block kernels (internal).
 #pragma once
+#include <stdlib.h>
+
 #include "dc_common.h"
 
 namespace dc {
@@ -10,6 +12,60 @@ constexpr int BN = 128;           // block tile = (64*MB) x 128, 2x2 waves of (3
 constexpr int kMaxSeg = DC_MAX_SEG;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using s16x4 = __attribute__((ext_vector_type(4))) short;
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+// f32x4, u32x4, the LDS-DMA casts DC_DMA_SRC / DC_DMA_DST, DC_WAITVM, lds_addr, lds_barrier and f32_to_bf16_rne: dc_common.h
+
+// 128-byte LDS rows of 8 pieces of 16 bytes: piece q of row r sits at position q ^ lds_row_swz(r) - conflict-free
+// ds_read_b128 fragment reads and ds_write_b64 plane stores (derivation: dc_dense_h2w.hip)
+__device__ __forceinline__ int lds_row_swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 1); }
+
+// exact fp32 -> three bf16: x = hi + mid + lo (8 + 8 + 8 significant bits)
+__device__ __forceinline__ void split1(float x, __bf16 &hi, __bf16 &mid, __bf16 &lo) {
+    hi = (__bf16)x;
+    const float r = x - (float)hi;        // exact
+    mid = (__bf16)r;
+    const float r2 = r - (float)mid;      // exact
+    lo = (__bf16)r2;
+}
+
+// four (already scaled) fp32 -> their two fp16 planes: x = h + l + O(2^-23 |x|)
+__device__ __forceinline__ void split4_h2(const float4 &v, f16x4 &h, f16x4 &l) {
+    const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const _Float16 a = (_Float16)x[i];
+        h[i] = a;
+        l[i] = (_Float16)(x[i] - (float)a);          // remainder is exact in fp32
+    }
+}
+
+// gfx950's transposing ds_read_b64_tr_b16 at a and four ROWB-byte rows further on: one 8-deep MFMA operand
+template <int ROWB>
+__device__ __forceinline__ bf16x8 tr_read(const char *a) {
+    const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(uintptr_t)(a));
+    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(uintptr_t)(a + 4 * ROWB));
+    union { s16x4 s[2]; bf16x8 b; } u;
+    u.s[0] = lo4, u.s[1] = hi4;
+    return u.b;
+}
+// one MFMA operand (8 consecutive k for column m0 + (lane & 31)) from a [k][m] plane image with rows of ROWB bytes
+template <int ROWB>
+__device__ __forceinline__ bf16x8 tr_operand(const char *plane, int m0) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+    const int h = g >> 1;
+    return tr_read<ROWB>(plane + (8 * h + q) * ROWB + (m0 + 16 * (g & 1) + 4 * pp) * 2);
+}
+
+// host side of the launchers (al16: dc_common.h)
+inline int env_int(const char *name, int dflt) {
+    const char *v = getenv(name);
+    return (v && *v) ? atoi(v) : dflt;
+}
 
 struct Mat {
     const float *p;
@@ -115,7 +171,8 @@ __device__ __forceinline__ unsigned h2_exp(float m) {
 __device__ __forceinline__ float h2_scale(float m) { return __uint_as_float((268u - h2_exp(m)) << 23); }
 __device__ __forceinline__ float h2_unscale(float m) { return __uint_as_float((h2_exp(m) - 14u) << 23); }
 
-// max of v[beg..end) over a 256-thread block (every thread gets the result); `red` = 4 floats of LDS
+// max of v[beg..end) over a 256-thread block (every thread gets the result); `red` = 4 floats of LDS.  The reduction is
+// block_reduce_max of dc_attn.hip written out: calling one shared function changed k_dw_h2w's register allocation
 __device__ __forceinline__ float h2_block_max(const float *v, int64_t beg, int64_t end, float *red) {
     float m = 0.f;
     for (int64_t i = beg + threadIdx.x; i < end; i += 256) m = fmaxf(m, v[i]);
@@ -232,6 +289,24 @@ bool fwd_h2_launch(const FwdParams &p, int mb, hipStream_t hs);
 bool fwd_h2w_launch(const FwdParams &p, hipStream_t hs);
 // the same tiles with both operands by LDS-DMA and the waves split by role (dc_dense_h2d.hip); tried first by fwd_h2w_launch
 bool fwd_h2d_launch(const FwdParams &p, hipStream_t hs);
+// weight preparation (dc_dense_prep.hip): one launch writes the row maxima and the scaled fp16x2 images of a layer's
+// weights and of their transposes
+struct WPrepParams {
+    const float *w[kMaxSeg];
+    int nseg;
+    int64_t Fo, Fi;
+    float *w_rowmax, *wt_rowmax;
+    _Float16 *wimg, *wtimg;
+    float *zero;                         // optional: a float buffer this launch also clears (dc_tag_weight_prep_zero)
+    int64_t zero_n;
+    int tall;                            // the transposed half is done by k_wt_colmax + k_wt_image (tall matrices): this
+                                         // launch only clears wt_rowmax for their atomic maxima
+};
+struct WPrepGroups {
+    WPrepParams g[kMaxGroups];
+};
+// k_weight_prep_grouped: grid (blocks, ngroups), block y prepares q.g[y]
+void weight_prep_grouped_launch(const WPrepGroups &q, int64_t blocks, int ngroups, hipStream_t hs);
 // wt[s][f][o] = ws[s][o][f]
 void transpose_weights_launch(const float *const *ws, int nseg, int64_t Fo, int64_t Fi, float *wt,
                               hipStream_t hs);

@@ -18,11 +18,7 @@
 // position q ^ ((r >> 2) & 3)) applied on the GLOBAL side of the DMA.
 #include "dc_dense.h"
 
-#include <stdlib.h>
-
 namespace dc {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 constexpr int kBfBK = 32;        // k per stage (bf16 elements): 64 bytes per row
 constexpr int kBfSlots = 4;      // ring depth
@@ -36,13 +32,6 @@ struct Bf16Params {
     int64_t lda, ldo, N, K, Fo;
     int relu, out_bf16;
 };
-
-__device__ __forceinline__ uint16_t f32_to_bf16_rne_d(float f) {
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // quiet NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 
 __global__ void __launch_bounds__(512)
 k_fwd_bf16(Bf16Params p) {
@@ -84,12 +73,10 @@ k_fwd_bf16(Bf16Params p) {
         auto dma = [&](int slot) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                __builtin_amdgcn_global_load_lds(
-                    (const void __attribute__((address_space(1))) *)(baseA + offA[q]),
-                    (void __attribute__((address_space(3))) *)(sA[slot] + (lw * 32 + q * 16) * 64), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds(
-                    (const void __attribute__((address_space(1))) *)(baseB + offB[q]),
-                    (void __attribute__((address_space(3))) *)(sB[slot] + (lw * 32 + q * 16) * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(DC_DMA_SRC(baseA + offA[q]),
+                                                 DC_DMA_DST(sA[slot] + (lw * 32 + q * 16) * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(DC_DMA_SRC(baseB + offB[q]),
+                                                 DC_DMA_DST(sB[slot] + (lw * 32 + q * 16) * 64), 16, 0, 0);
             }
             baseA += kBfBK;
             baseB += kBfBK;
@@ -100,9 +87,9 @@ k_fwd_bf16(Bf16Params p) {
             // them pending here) are still in flight; the barrier publishes stage `it` and tells the
             // loaders that the MFMA waves are done with stage it - 1, whose slot then takes stage it + 3
             const int later = nst - 1 - it;
-            if (later >= 2) __builtin_amdgcn_s_waitcnt(0x0F70 | 8);        // vmcnt(8)
-            else if (later == 1) __builtin_amdgcn_s_waitcnt(0x0F70 | 4);   // vmcnt(4)
-            else __builtin_amdgcn_s_waitcnt(0x0F70 | 0);                   // vmcnt(0)
+            if (later >= 2) DC_WAITVM(8);
+            else if (later == 1) DC_WAITVM(4);
+            else DC_WAITVM(0);
             __builtin_amdgcn_s_barrier();
             if (it + kBfAhead < nst) dma((it + kBfAhead) & (kBfSlots - 1));
         }
@@ -158,7 +145,7 @@ k_fwd_bf16(Bf16Params p) {
         if (row < p.N && col < p.Fo) {
             v += bcol[(c >> 5) & 1];
             if (relu) v = fmaxf(v, 0.f);
-            if (p.out_bf16) ((uint16_t *)p.out)[row * p.ldo + col] = f32_to_bf16_rne_d(v);
+            if (p.out_bf16) ((uint16_t *)p.out)[row * p.ldo + col] = f32_to_bf16_rne(v);
             else ((float *)p.out)[row * p.ldo + col] = v;
         }
     });
@@ -216,10 +203,8 @@ k_fwd_bf16x(Bf16Params p) {
         char *ta = lds + (2 * slot) * kGxTile, *tb = ta + kGxTile;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(baseA + offA[j]),
-                                             (void __attribute__((address_space(3))) *)(ta + (2 * wid + j) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(baseB + offB[j]),
-                                             (void __attribute__((address_space(3))) *)(tb + (2 * wid + j) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(DC_DMA_SRC(baseA + offA[j]), DC_DMA_DST(ta + (2 * wid + j) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(DC_DMA_SRC(baseB + offB[j]), DC_DMA_DST(tb + (2 * wid + j) * 1024), 16, 0, 0);
         }
         baseA += kGxBK;
         baseB += kGxBK;
@@ -251,9 +236,9 @@ k_fwd_bf16x(Bf16Params p) {
         // them issued so far) are outstanding; the barrier publishes every wave's pieces and says that everybody is
         // done with stage it - 1, whose slot then takes stage it + 3
         const int later = nst - 1 - it;
-        if (later >= 2) __builtin_amdgcn_s_waitcnt(0x0F70 | 8);            // vmcnt(8)
-        else if (later == 1) __builtin_amdgcn_s_waitcnt(0x0F70 | 4);       // vmcnt(4)
-        else __builtin_amdgcn_s_waitcnt(0x0F70 | 0);                       // vmcnt(0)
+        if (later >= 2) DC_WAITVM(8);
+        else if (later == 1) DC_WAITVM(4);
+        else DC_WAITVM(0);
         __builtin_amdgcn_s_barrier();
         if (it + kGxAhead < nst) stage((it + kGxAhead) & (kGxSlots - 1));
         const char *ta = lds + (2 * (it & (kGxSlots - 1))) * kGxTile, *tb = ta + kGxTile;
@@ -302,7 +287,7 @@ k_fwd_bf16x(Bf16Params p) {
                         const int rl = rbase + mb * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
                         float v = acc[mb][nb][reg] + bcol;
                         if (relu) v = fmaxf(v, 0.f);
-                        if (OUT_BF16) *reinterpret_cast<uint16_t *>(dst + rl * rs) = f32_to_bf16_rne_d(v);
+                        if (OUT_BF16) *reinterpret_cast<uint16_t *>(dst + rl * rs) = f32_to_bf16_rne(v);
                         else *reinterpret_cast<float *>(dst + rl * rs) = v;
                     }
             }
@@ -341,7 +326,7 @@ k_to_bf16(const float *const *src, int nseg, int64_t rows, int64_t cols, int64_t
     if (i >= per * nseg) return;
     const int s = (int)(i / per);
     const int64_t r = (i % per) / cols, c = (i % per) % cols;
-    dst[r * ld_dst + s * cols + c] = f32_to_bf16_rne_d(src[s][r * ld_src + c]);
+    dst[r * ld_dst + s * cols + c] = f32_to_bf16_rne(src[s][r * ld_src + c]);
 }
 
 struct PtrPack { const float *p[kMaxSeg]; };
@@ -354,7 +339,7 @@ k_to_bf16_pack(PtrPack src, int nseg, int64_t rows, int64_t cols, int64_t ld_src
     if (i >= per * nseg) return;
     const int s = (int)(i / per);
     const int64_t r = (i % per) / cols, c = (i % per) % cols;
-    dst[r * ld_dst + s * cols + c] = f32_to_bf16_rne_d(src.p[s][r * ld_src + c]);
+    dst[r * ld_dst + s * cols + c] = f32_to_bf16_rne(src.p[s][r * ld_src + c]);
 }
 
 
@@ -378,7 +363,7 @@ k_mask_grad_bf16(MaskBf16Params p) {
     if (row >= p.N) return;
     float v = ld_elem(p.g, row * p.ldg + c, p.g_bf16);
     if (p.mask && !(ld_elem(p.mask, row * p.ldm + c, p.mask_bf16) > 0.f)) v = 0.f;
-    p.gm[row * p.ldgm + c] = f32_to_bf16_rne_d(v);
+    p.gm[row * p.ldgm + c] = f32_to_bf16_rne(v);
 }
 
 // The same with 8 columns per thread and 16-byte accesses (F, the leading dimensions and the pointers allow it whenever
@@ -414,7 +399,7 @@ k_mask_grad_bf16x8(MaskBf16Params p) {
     }
     uint32_t o[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (uint32_t)f32_to_bf16_rne_d(v[2 * j]) | ((uint32_t)f32_to_bf16_rne_d(v[2 * j + 1]) << 16);
+    for (int j = 0; j < 4; ++j) o[j] = (uint32_t)f32_to_bf16_rne(v[2 * j]) | ((uint32_t)f32_to_bf16_rne(v[2 * j + 1]) << 16);
     *reinterpret_cast<uint4 *>(p.gm + row * p.ldgm + c) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
@@ -425,20 +410,6 @@ k_mask_grad_bf16x8(MaskBf16Params p) {
 constexpr int kDwbK = 32;
 constexpr int kDwbRowA = 128 * 2 + 64, kDwbRowB = 256 * 2 + 64;        // bytes per node row of the g / x image
 constexpr int kDwbStage = kDwbK * (kDwbRowA + kDwbRowB);                // 28,672 B
-
-using dwb_s16x4 = __attribute__((ext_vector_type(4))) short;
-typedef __attribute__((address_space(3))) dwb_s16x4 dwb_lds_s16x4;
-template <int ROWB>
-__device__ __forceinline__ bf16x8 dwb_tr_operand(const char *plane, int m0) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-    const int h = g >> 1;
-    const char *a = plane + (8 * h + q) * ROWB + (m0 + 16 * (g & 1) + 4 * pp) * 2;
-    const dwb_s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((dwb_lds_s16x4 *)(uintptr_t)(a));
-    const dwb_s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((dwb_lds_s16x4 *)(uintptr_t)(a + 4 * ROWB));
-    union { dwb_s16x4 s[2]; bf16x8 b; } u;
-    u.s[0] = lo4, u.s[1] = hi4;
-    return u.b;
-}
 
 __global__ void __launch_bounds__(512)
 k_dw_bf16(DwBf16Params p) {
@@ -495,10 +466,10 @@ k_dw_bf16(DwBf16Params p) {
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 fa[2], fb[2];
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb) fa[mb] = dwb_tr_operand<kDwbRowA>(buf + ks * 16 * kDwbRowA, wm * 64 + mb * 32);
+            for (int mb = 0; mb < 2; ++mb) fa[mb] = tr_operand<kDwbRowA>(buf + ks * 16 * kDwbRowA, wm * 64 + mb * 32);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
-                fb[nb] = dwb_tr_operand<kDwbRowB>(buf + kDwbK * kDwbRowA + ks * 16 * kDwbRowB, wn * 64 + nb * 32);
+                fb[nb] = tr_operand<kDwbRowB>(buf + kDwbK * kDwbRowA + ks * 16 * kDwbRowB, wn * 64 + nb * 32);
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -568,19 +539,13 @@ k_dw_bf16(DwBf16Params p) {
 constexpr int kDwdSlots = 6, kDwdAhead = 5;
 constexpr int kDwdRowA = 128 * 2, kDwdRowB = 256 * 2;                    // dense node rows of the g / x image
 constexpr int kDwdStage = kDwbK * (kDwdRowA + kDwdRowB);                 // 24,576 B
-#define DC_DWD_WAITVM(n) __builtin_amdgcn_s_waitcnt(0x0F70 | ((n) & 15) | (((n) >> 4) << 14))   // s_waitcnt vmcnt(n) only
 
 template <int ROWB>
 __device__ __forceinline__ bf16x8 dwd_tr_operand(const char *plane, int m0) {
     const int lane = threadIdx.x & 63, g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
     const int h = g >> 1;
     // node rows 8 h + q and + 4 (both have node & 3 = q), column chunk m0 / 32 stored at chunk ^ q
-    const char *a = plane + (8 * h + q) * ROWB + (((m0 >> 5) ^ q) << 6) + 32 * (g & 1) + 8 * pp;
-    const dwb_s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((dwb_lds_s16x4 *)(uintptr_t)(a));
-    const dwb_s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((dwb_lds_s16x4 *)(uintptr_t)(a + 4 * ROWB));
-    union { dwb_s16x4 s[2]; bf16x8 b; } u;
-    u.s[0] = lo4, u.s[1] = hi4;
-    return u.b;
+    return tr_read<ROWB>(plane + (8 * h + q) * ROWB + (((m0 >> 5) ^ q) << 6) + 32 * (g & 1) + 8 * pp);
 }
 
 __global__ void __launch_bounds__(768)
@@ -627,15 +592,14 @@ k_dw_bf16d(DwBf16Params p) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int c = 2 * w + j;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rg_, (void __attribute__((address_space(3))) *)(dst + c * 1024), 16,
-                                                             voffg, c * gstep + st * gstage, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rg_, DC_DMA_DST(dst + c * 1024), 16, voffg,
+                                                             c * gstep + st * gstage, 0, 0);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int c = 4 * w + j;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                        rx_, (void __attribute__((address_space(3))) *)(dst + kDwbK * kDwdRowA + c * 1024), 16, voffx[j & 1],
-                        c * xstep + st * xstage, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx_, DC_DMA_DST(dst + kDwbK * kDwdRowA + c * 1024), 16, voffx[j & 1],
+                                                             c * xstep + st * xstage, 0, 0);
                 }
             };
 #pragma unroll
@@ -644,11 +608,11 @@ k_dw_bf16d(DwBf16Params p) {
             for (int it = 0; it < nst; ++it) {
                 // all but the stages after `it` (at most kDwdAhead - 1 of them, 6 instructions each) have landed
                 const int later = nst - 1 - it;
-                if (later >= 4) DC_DWD_WAITVM(24);
-                else if (later == 3) DC_DWD_WAITVM(18);
-                else if (later == 2) DC_DWD_WAITVM(12);
-                else if (later == 1) DC_DWD_WAITVM(6);
-                else DC_DWD_WAITVM(0);
+                if (later >= 4) DC_WAITVM(24);
+                else if (later == 3) DC_WAITVM(18);
+                else if (later == 2) DC_WAITVM(12);
+                else if (later == 1) DC_WAITVM(6);
+                else DC_WAITVM(0);
                 __builtin_amdgcn_s_barrier();            // publishes stage it; the MFMA waves have left stage it - 1
                 if (it + kDwdAhead < nst) stage(it + kDwdAhead);
             }

@@ -269,7 +269,6 @@ k_dw_fast(DwParams p) {
     }
 }
 
-static inline bool al16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
 bool fwd_fast_launch(const FwdParams &p, int mb, hipStream_t hs) {
     if (p.Fi % BK != 0 || p.Fi < BK) return false;

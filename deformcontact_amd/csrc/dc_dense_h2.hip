@@ -19,24 +19,15 @@
 
 namespace dc {
 
-using h2_f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-using h2_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 constexpr int kH2Plane = 32;                      // bytes per plane inside an LDS row (16 fp16)
 constexpr int kH2Row = 2 * kH2Plane + 16;         // 80 B: conflict-free b64 stores / b128 reads
 
 __device__ __forceinline__ void h2_split_store(char *dst, float4 x, float s) {
     x = make_float4(x.x * s, x.y * s, x.z * s, x.w * s);
-    h2_f16x4 h, l;
-    const float v[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const _Float16 a = (_Float16)v[i];
-        h[i] = a;
-        l[i] = (_Float16)(v[i] - (float)a);
-    }
-    *reinterpret_cast<h2_f16x4 *>(dst) = h;
-    *reinterpret_cast<h2_f16x4 *>(dst + kH2Plane) = l;
+    f16x4 h, l;
+    split4_h2(x, h, l);
+    *reinterpret_cast<f16x4 *>(dst) = h;
+    *reinterpret_cast<f16x4 *>(dst + kH2Plane) = l;
 }
 
 template <int MB, bool BDMA>
@@ -124,9 +115,8 @@ k_fwd_h2(FwdParams p) {
     auto dma_b = [&](int b) {                         // B of the NEXT stage straight into buffer b
 #pragma unroll
         for (int q = 0; q < 2; ++q)
-            __builtin_amdgcn_global_load_lds(
-                (const void __attribute__((address_space(1))) *)(baseB + dmaOff[q]),
-                (void __attribute__((address_space(3))) *)(sB + b * kSzB + (wid * 32 + q * 16) * 64), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(DC_DMA_SRC(baseB + dmaOff[q]),
+                                             DC_DMA_DST(sB + b * kSzB + (wid * 32 + q * 16) * 64), 16, 0, 0);
         baseB += BK;
     };
     auto store = [&](int b) {
@@ -148,21 +138,21 @@ k_fwd_h2(FwdParams p) {
             const int rowl = wn * 64 + nb * 32 + fr;
             fragBd[nb][pl] = kOffB + rowl * 64 + 16 * ((2 * pl + fh) ^ ((rowl >> 2) & 3));
         }
-    h2_f16x8 fa[MB][2], fb[2][2];
+    f16x8 fa[MB][2], fb[2][2];
     auto frags = [&](int b) {
         const char *buf = sB + b * kSzB;
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl)
-                fa[mb][pl] = *reinterpret_cast<const h2_f16x8 *>(sA + b * kSzA + fragA + mb * 32 * kH2Row +
+                fa[mb][pl] = *reinterpret_cast<const f16x8 *>(sA + b * kSzA + fragA + mb * 32 * kH2Row +
                                                                  pl * kH2Plane);
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl)
-                fb[nb][pl] = BDMA ? *reinterpret_cast<const h2_f16x8 *>(buf + fragBd[nb][pl])
-                                  : *reinterpret_cast<const h2_f16x8 *>(buf + fragB + nb * 32 * kH2Row +
+                fb[nb][pl] = BDMA ? *reinterpret_cast<const f16x8 *>(buf + fragBd[nb][pl])
+                                  : *reinterpret_cast<const f16x8 *>(buf + fragB + nb * 32 * kH2Row +
                                                                           pl * kH2Plane);
     };
     auto mma = [&]() {
@@ -242,10 +232,6 @@ k_fwd_h2(FwdParams p) {
     });
 }
 
-
-
-static inline bool h2_al16(const void *q) { return ((uintptr_t)q & 15) == 0; }
-
 bool fwd_h2_launch(const FwdParams &p, int mb, hipStream_t hs) {
     if (!p.h2.a_rowmax || !p.h2.b_rowmax || p.nseg != 1) return false;
     if (fwd_h2w_launch(p, hs)) return true;
@@ -253,7 +239,7 @@ bool fwd_h2_launch(const FwdParams &p, int mb, hipStream_t hs) {
     // 32-bit per-thread offsets: a block touches 128 rows of each operand
     if (p.x[0].ld * 128 >= ((int64_t)1 << 30) || p.Fi * 128 >= ((int64_t)1 << 30)) return false;
     for (int s = 0; s < p.nseg; ++s)
-        if (!h2_al16(p.x[s].p) || !h2_al16(p.w[s].p) || p.x[s].ld % 4 != 0 || p.x[s].ld != p.x[0].ld)
+        if (!al16(p.x[s].p) || !al16(p.w[s].p) || p.x[s].ld % 4 != 0 || p.x[s].ld != p.x[0].ld)
             return false;
     const int64_t grid = ((p.N + 64 * mb - 1) / (64 * mb)) * ((p.Fo + BN - 1) / BN) *
                          (p.ksplit > 1 ? p.ksplit : 1);

@@ -20,16 +20,13 @@
 //   * The epilogue costs 7.6 us as 4-byte stores from the accumulator layout (two 128-byte runs per instruction);
 //     here the accumulators go through the (now free) LDS and leave as one 1-KiB row per store instruction, the row
 //     / column factors and the bias staged beside them by a loading wave that fetched them at the start: 3.2 us.
-// LDS images: rows of 128 bytes = 8 pieces of 16 bytes, piece q of row r at position q ^ F(r) (F as in
+// LDS images: rows of 128 bytes = 8 pieces of 16 bytes, piece q of row r at position q ^ F(r) (F = lds_row_swz, as in
 // dc_dense_h2w.hip: conflict-free ds_read_b128 fragment reads); an LDS-DMA instruction writes 1 KiB lane-linear
 // (8 rows), so the swizzle is applied to the per-lane SOURCE address.  x pieces: q = k / 4 (fp32); weight pieces:
 // q = 4 * kstep + 2 * plane + half (dc_tag_weight_prep's record order).
 #include "dc_dense.h"
 
 namespace dc {
-
-using hd_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using hd_f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kDBM = 128, kDBN = 256, kDBK = 32;
 constexpr int kDRow = 128;                              // bytes per LDS row (both operands)
@@ -40,8 +37,6 @@ constexpr int kDLds = kDRW * kDSzB + kDRX * kDSzA;      // 160 KB
 constexpr int kDOffRowF = kDBM * 1024, kDOffColF = kDOffRowF + kDBM * 4, kDOffBias = kDOffColF + kDBN * 4;
 static_assert(kDLds <= 160 * 1024 && kDOffBias + kDBN * 4 <= kDLds, "LDS budget");
 
-__device__ __forceinline__ int hd_swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 1); }
-#define DC_HD_WAITVM(n) __builtin_amdgcn_s_waitcnt(0x0F70 | ((n) & 15) | (((n) >> 4) << 14))   // s_waitcnt vmcnt(n) only
 
 template <bool FULL>
 __global__ void __launch_bounds__(512)
@@ -69,15 +64,15 @@ k_fwd_h2d(FwdParams p) {
     auto store_rows = [&]() {
         __syncthreads();
         const bool relu = p.relu != 0;
-        const hd_f32x4 icol = *reinterpret_cast<const hd_f32x4 *>(lds + kDOffColF + 16 * lane);
-        const hd_f32x4 bcol = *reinterpret_cast<const hd_f32x4 *>(lds + kDOffBias + 16 * lane);
+        const f32x4 icol = *reinterpret_cast<const f32x4 *>(lds + kDOffColF + 16 * lane);
+        const f32x4 bcol = *reinterpret_cast<const f32x4 *>(lds + kDOffBias + 16 * lane);
         const int64_t col = col0 + 4 * lane;
 #pragma unroll 4
         for (int j = 0; j < 16; ++j) {
             const int rl = wid * 16 + j;
             const int64_t row = row0 + rl;
             const float sv = *reinterpret_cast<const float *>(lds + kDOffRowF + 4 * rl);
-            hd_f32x4 v = *reinterpret_cast<const hd_f32x4 *>(lds + rl * 1024 + 16 * lane);
+            f32x4 v = *reinterpret_cast<const f32x4 *>(lds + rl * 1024 + 16 * lane);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float t = (v[i] * sv) * icol[i];
@@ -85,7 +80,7 @@ k_fwd_h2d(FwdParams p) {
                 if (relu) t = fmaxf(t, 0.f);
                 v[i] = row >= data_end ? 0.f : t;             // padding rows of a grouped launch stay zero rows
             }
-            if (FULL || (row < p.N && col < p.Fo)) *reinterpret_cast<hd_f32x4 *>(p.out + row * p.ldo + col) = v;
+            if (FULL || (row < p.N && col < p.Fo)) *reinterpret_cast<f32x4 *>(p.out + row * p.ldo + col) = v;
         }
     };
 
@@ -104,13 +99,13 @@ k_fwd_h2d(FwdParams p) {
         int voff[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e)
-            voff[e] = (int)(((int64_t)(lane >> 3) * ld) * 4 + 16 * ((lane & 7) ^ hd_swz(8 * e + (lane >> 3))));
+            voff[e] = (int)(((int64_t)(lane >> 3) * ld) * 4 + 16 * ((lane & 7) ^ lds_row_swz(8 * e + (lane >> 3))));
         const int cstep = (int)(8 * ld * 4);           // bytes from one chunk's rows to the next chunk's
         if (isx) {
             // wave 6 also owns the epilogue's factors: 2 rows and 4 columns per lane, fetched now, written to LDS once
             // the rings are free
             float rowf[2] = {0.f, 0.f};
-            hd_f32x4 colf = {0.f, 0.f, 0.f, 0.f}, biasv = {0.f, 0.f, 0.f, 0.f};
+            f32x4 colf = {0.f, 0.f, 0.f, 0.f}, biasv = {0.f, 0.f, 0.f, 0.f};
             if (w == 0) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
@@ -130,7 +125,7 @@ k_fwd_h2d(FwdParams p) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int c = 8 * w + j;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (void __attribute__((address_space(3))) *)(dst + c * 1024), 16,
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, DC_DMA_DST(dst + c * 1024), 16,
                                                              voff[j & 1], c * cstep + s * (kDBK * 4), 0, 0);
                 }
             };
@@ -139,22 +134,22 @@ k_fwd_h2d(FwdParams p) {
 #pragma unroll
             for (int s = 0; s < kDRX - 1; ++s)
                 if (s < nst) stage(s);
-            if (nst > kDRX - 1) DC_HD_WAITVM(8 * (kDRX - 3)); else DC_HD_WAITVM(0);      // stages 0 and 1
+            if (nst > kDRX - 1) DC_WAITVM(8 * (kDRX - 3)); else DC_WAITVM(0);      // stages 0 and 1
             __builtin_amdgcn_s_barrier();              // P
             int it = 0;
             for (; it + kDRX - 1 < nst; ++it) {
                 stage(it + kDRX - 1);
-                DC_HD_WAITVM(8 * (kDRX - 3));          // stage it + 2
+                DC_WAITVM(8 * (kDRX - 3));          // stage it + 2
                 __builtin_amdgcn_s_barrier();
             }
             for (; it < nst; ++it) {
-                DC_HD_WAITVM(0);
+                DC_WAITVM(0);
                 __builtin_amdgcn_s_barrier();
             }
             if (w == 0) {
                 *reinterpret_cast<float2 *>(lds + kDOffRowF + 8 * lane) = make_float2(rowf[0], rowf[1]);
-                *reinterpret_cast<hd_f32x4 *>(lds + kDOffColF + 16 * lane) = colf;
-                *reinterpret_cast<hd_f32x4 *>(lds + kDOffBias + 16 * lane) = biasv;
+                *reinterpret_cast<f32x4 *>(lds + kDOffColF + 16 * lane) = colf;
+                *reinterpret_cast<f32x4 *>(lds + kDOffBias + 16 * lane) = biasv;
             }
         } else {
             auto stage = [&](int s) {                  // 16 instructions per wave: chunks 16 w .. 16 w + 15 of 32
@@ -162,17 +157,17 @@ k_fwd_h2d(FwdParams p) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
                     const int c = 16 * w + j;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (void __attribute__((address_space(3))) *)(dst + c * 1024), 16,
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, DC_DMA_DST(dst + c * 1024), 16,
                                                              voff[j & 1], c * cstep + s * (kDBK * 4), 0, 0);
                 }
             };
             stage(0);
             if (nst > 1) stage(1);
-            DC_HD_WAITVM(0);
+            DC_WAITVM(0);
             __builtin_amdgcn_s_barrier();              // P
             for (int it = 0; it < nst; ++it) {
                 if (it + 2 < nst) stage(it + 2);       // into the slot stage it - 1 left at the last barrier
-                DC_HD_WAITVM(0);
+                DC_WAITVM(0);
                 __builtin_amdgcn_s_barrier();
             }
         }
@@ -182,7 +177,7 @@ k_fwd_h2d(FwdParams p) {
 
     // ---------------------------------------------------------------------- MFMA waves 0-3, 64 x 128 each
     const int wm = wid >> 1, wn = wid & 1;
-    const int fr = lane & 31, fh = lane >> 5, fsw = hd_swz(fr);
+    const int fr = lane & 31, fh = lane >> 5, fsw = lds_row_swz(fr);
     const int fragA = (wm * 64 + fr) * kDRow, fragB0 = (wn * 128 + fr) * kDRow;
     float scA[2];
 #pragma unroll
@@ -199,26 +194,26 @@ k_fwd_h2d(FwdParams p) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[mb][nb][i] = 0.f;
     // x fragment of k-step ks, row block mb: k = 16 ks + 8 fh .. + 7 of row fr = pieces 4 ks + 2 fh and + 1 (fp32)
-    hd_f32x4 ra[2][2];                                 // raw, one k-step: [mb][piece]
-    hd_f16x8 fa0[2][2], fa1[2][2], fb[4][2];           // x planes: two sets (k-steps alternate); weights: ONE set
+    f32x4 ra[2][2];                                 // raw, one k-step: [mb][piece]
+    f16x8 fa0[2][2], fa1[2][2], fb[4][2];           // x planes: two sets (k-steps alternate); weights: ONE set
     auto rawA = [&](int slot, int ks) {
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                ra[mb][h] = *reinterpret_cast<const hd_f32x4 *>(sA + slot * kDSzA + fragA + mb * 32 * kDRow +
+                ra[mb][h] = *reinterpret_cast<const f32x4 *>(sA + slot * kDSzA + fragA + mb * 32 * kDRow +
                                                                 16 * ((4 * ks + 2 * fh + h) ^ fsw));
     };
     auto fragB = [&](int nb, int slot, int ks) {
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
-            fb[nb][pl] = *reinterpret_cast<const hd_f16x8 *>(sB + slot * kDSzB + fragB0 + nb * 32 * kDRow +
+            fb[nb][pl] = *reinterpret_cast<const f16x8 *>(sB + slot * kDSzB + fragB0 + nb * 32 * kDRow +
                                                              16 * ((4 * ks + 2 * pl + fh) ^ fsw));
     };
-    auto split = [&](hd_f16x8 (&fa)[2][2], int mb) {   // the scaled value's two fp16 planes, as k_fwd_h2w's staging
+    auto split = [&](f16x8 (&fa)[2][2], int mb) {   // the scaled value's two fp16 planes, as k_fwd_h2w's staging
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const hd_f32x4 v = ra[mb][h] * scA[mb];
+            const f32x4 v = ra[mb][h] * scA[mb];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const _Float16 a = (_Float16)v[i];
@@ -233,14 +228,14 @@ k_fwd_h2d(FwdParams p) {
     // timing-only ablation (wrong results by construction; tools/r06/mfma16_abl.sh): every 32x32x16 MFMA replaced by two
     // 16x16x32 ones on the same operand registers and two quarters of the same accumulator - same FLOPs, same LDS reads, same
     // VALU: does the chip hold a higher clock on the smaller MFMA shape inside THIS loop (MI355X_MICROARCH.md, DVFS item 7)?
-    hd_f32x4 acc4[2][4][4];
+    f32x4 acc4[2][4][4];
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc4[mb][nb][q] = hd_f32x4{0.f, 0.f, 0.f, 0.f};
-    auto mma_nb = [&](const hd_f16x8 (&fa)[2][2], int nb) {
+            for (int q = 0; q < 4; ++q) acc4[mb][nb][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto mma_nb = [&](const f16x8 (&fa)[2][2], int nb) {
         constexpr int pa[3] = {1, 0, 0}, pb[3] = {0, 1, 0};
 #pragma unroll
         for (int t = 0; t < 3; ++t)
@@ -251,7 +246,7 @@ k_fwd_h2d(FwdParams p) {
             }
     };
 #else
-    auto mma_nb = [&](const hd_f16x8 (&fa)[2][2], int nb) {
+    auto mma_nb = [&](const f16x8 (&fa)[2][2], int nb) {
         constexpr int pa[3] = {1, 0, 0}, pb[3] = {0, 1, 0};
 #pragma unroll
         for (int t = 0; t < 3; ++t)
@@ -335,7 +330,6 @@ k_fwd_h2d(FwdParams p) {
     store_rows();
 }
 
-static inline bool hd_al16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
 // eligible: what fwd_h2w_launch takes, minus the split reduction, the exp epilogue and the correction operand (those stay
 // with k_fwd_h2w), plus 16-byte rows on the output side
@@ -353,9 +347,9 @@ bool fwd_h2d_launch(const FwdParams &p, hipStream_t hs) {
         return (v && *v) ? atoi(v) : 8 * kDBK;
     }();
     if (p.Fi % kDBK != 0 || p.Fi < kDBK || p.Fi < min_k || p.Fo % 4 != 0 || p.ldo % 4 != 0 || p.x[0].ld % 4 != 0) return false;
-    if (!hd_al16(p.x[0].p) || !hd_al16(p.w[0].p) || !hd_al16(p.out)) return false;
+    if (!al16(p.x[0].p) || !al16(p.w[0].p) || !al16(p.out)) return false;
     for (int g = 0; g < p.grp.n; ++g)
-        if (!hd_al16(p.grp.w[g])) return false;
+        if (!al16(p.grp.w[g])) return false;
     // buffer descriptors: 32-bit byte counts per tile
     if (p.x[0].ld * kDBM >= ((int64_t)1 << 28) || p.Fi * kDBN >= ((int64_t)1 << 28)) return false;
     const int64_t tiles = ((p.N + kDBM - 1) / kDBM) * ((p.Fo + kDBN - 1) / kDBN);

@@ -21,24 +21,17 @@
 // register sets) and written during stage it+1 into a ring of three LDS stage buffers, so that stage it+1 is
 // complete one barrier before it is computed and its first fragments can be read under the last MFMAs of
 // stage it (two fragment register sets).  LDS rows are 128 bytes = 8 pieces of 16 bytes (piece q = 4*kstep
-// + 2*plane + half); piece q of row r sits at position q ^ F(r), F(r) = ((r >> 1) & 7) ^ 2*(r & 1):
-// conflict-free ds_read_b128 fragment reads (each 16-lane group sees 8 even and 8 odd rows with 8 distinct
-// F each) and conflict-free ds_write_b64 of the split x (two adjacent rows per 16-lane group land on
+// + 2*plane + half); piece q of row r sits at position q ^ F(r), F(r) = ((r >> 1) & 7) ^ 2*(r & 1) (lds_row_swz
+// in dc_dense.h): conflict-free ds_read_b128 fragment reads (each 16-lane group sees 8 even and 8 odd rows with
+// 8 distinct F each) and conflict-free ds_write_b64 of the split x (two adjacent rows per 16-lane group land on
 // disjoint pieces).
 #include "dc_dense.h"
 
 namespace dc {
 
-using hw_f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-using hw_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using hw_f32x4 = __attribute__((ext_vector_type(4))) float;
-using hw_u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
 constexpr int kWBM = 128, kWBN = 256, kWBK = 32;
 constexpr int kWRow = 128;                              // bytes per LDS row (both operands)
 constexpr int kWSzA = kWBM * kWRow, kWSzB = kWBN * kWRow;
-
-__device__ __forceinline__ int hw_swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 1); }
 
 // CORR: the left operand is x - x2_coef[row] * x2 (dc_tag_linear_fwd_h2p_corr); a template parameter so that the plain
 // kernel keeps its register allocation
@@ -78,7 +71,7 @@ k_fwd_h2w(FwdParams p) {
         row = (FULL || row < p.N) ? row : p.N - 1;
         offA[j] = (unsigned)((row - row0) * lda + 4 * k8);
         // this thread's 4 k: k-step k8 >> 2, half (k8 >> 1) & 1, 8-byte slot k8 & 1 of the piece
-        const int q = 4 * (k8 >> 2) + ((k8 >> 1) & 1), f = hw_swz(rl);
+        const int q = 4 * (k8 >> 2) + ((k8 >> 1) & 1), f = lds_row_swz(rl);
         ldsAh[j] = rl * kWRow + 16 * (q ^ f) + 8 * (k8 & 1);
         ldsAl[j] = rl * kWRow + 16 * ((q + 2) ^ f) + 8 * (k8 & 1);
         const float m = p.h2.a_rowmax[row];
@@ -92,7 +85,7 @@ k_fwd_h2w(FwdParams p) {
         int64_t col = col0 + rl;
         col = (FULL || col < p.Fo) ? col : p.Fo - 1;
         offB[j] = (unsigned)((col - col0) * p.Fi + 4 * k8);           // 4-byte units, 16 bytes per piece
-        ldsB[j] = rl * kWRow + 16 * (k8 ^ hw_swz(rl));
+        ldsB[j] = rl * kWRow + 16 * (k8 ^ lds_row_swz(rl));
     }
 
     f32x16 acc[2][2];
@@ -103,41 +96,41 @@ k_fwd_h2w(FwdParams p) {
     const float *baseA = p.x[0].p + row0 * lda + (int64_t)st_beg * kWBK;      // wave-uniform running bases
     const float *baseB = wimg + col0 * p.Fi + (int64_t)st_beg * kWBK;
     const float *baseA2 = CORR ? p.x2 + row0 * lda + (int64_t)st_beg * kWBK : nullptr;
-    hw_f32x4 va0[2], va1[2];                                          // two register sets, named: no runtime index
-    hw_f32x4 vc0[2], vc1[2];                                          // (CORR) the correction operand's pieces
-    hw_u32x4 vb0[4], vb1[4];
+    f32x4 va0[2], va1[2];                                          // two register sets, named: no runtime index
+    f32x4 vc0[2], vc1[2];                                          // (CORR) the correction operand's pieces
+    u32x4 vb0[4], vb1[4];
 
-    auto gload_set = [&](hw_f32x4 (&va)[2], hw_f32x4 (&vc)[2], hw_u32x4 (&vb)[4]) {
+    auto gload_set = [&](f32x4 (&va)[2], f32x4 (&vc)[2], u32x4 (&vb)[4]) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            va[j] = *reinterpret_cast<const hw_f32x4 *>(baseA + offA[j]);
+            va[j] = *reinterpret_cast<const f32x4 *>(baseA + offA[j]);
         if (CORR) {                                                       // (combined at LDS-store time: stays in flight)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) vc[j] = *reinterpret_cast<const hw_f32x4 *>(baseA2 + offA[j]);
+            for (int j = 0; j < 2; ++j) vc[j] = *reinterpret_cast<const f32x4 *>(baseA2 + offA[j]);
             baseA2 += kWBK;
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) vb[j] = *reinterpret_cast<const hw_u32x4 *>(baseB + offB[j]);
+        for (int j = 0; j < 4; ++j) vb[j] = *reinterpret_cast<const u32x4 *>(baseB + offB[j]);
         baseA += kWBK;
         baseB += kWBK;
     };
-    auto lstore_b = [&](const hw_u32x4 (&vb)[4], int b) {
+    auto lstore_b = [&](const u32x4 (&vb)[4], int b) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) *reinterpret_cast<hw_u32x4 *>(sB + b * kWSzB + ldsB[j]) = vb[j];
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<u32x4 *>(sB + b * kWSzB + ldsB[j]) = vb[j];
     };
-    auto lstore_a = [&](const hw_f32x4 (&va)[2], const hw_f32x4 (&vc)[2], int b) {
+    auto lstore_a = [&](const f32x4 (&va)[2], const f32x4 (&vc)[2], int b) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const hw_f32x4 v = (CORR ? va[j] - vc[j] * cA[j] : va[j]) * scA[j];
-            hw_f16x4 h, l;
+            const f32x4 v = (CORR ? va[j] - vc[j] * cA[j] : va[j]) * scA[j];
+            f16x4 h, l;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const _Float16 a = (_Float16)v[i];
+            for (int i = 0; i < 4; ++i) {                                   // split4_h2 written out: through its float4 the
+                const _Float16 a = (_Float16)v[i];                          // kernel's instruction schedule changed
                 h[i] = a;
                 l[i] = (_Float16)(v[i] - (float)a);
             }
-            *reinterpret_cast<hw_f16x4 *>(sA + b * kWSzA + ldsAh[j]) = h;
-            *reinterpret_cast<hw_f16x4 *>(sA + b * kWSzA + ldsAl[j]) = l;
+            *reinterpret_cast<f16x4 *>(sA + b * kWSzA + ldsAh[j]) = h;
+            *reinterpret_cast<f16x4 *>(sA + b * kWSzA + ldsAl[j]) = l;
         }
     };
     auto gload = [&](int set) {
@@ -153,27 +146,27 @@ k_fwd_h2w(FwdParams p) {
         lstoreB(set, b);
         lstoreA(set, b);
     };
-    const int fr = lane & 31, fh = lane >> 5, fsw = hw_swz(fr);
+    const int fr = lane & 31, fh = lane >> 5, fsw = lds_row_swz(fr);
     const int fragA = (wm * 64 + fr) * kWRow, fragB = (wn * 64 + fr) * kWRow;
     // fragment registers: two sets (one k-step each), so that the reads of the next k-step - also the first
     // one of the NEXT stage, whose buffer has been complete since the previous barrier - are in flight
     // under the MFMAs of the current one and no MFMA waits on LDS latency behind a barrier
-    hw_f16x8 fa0[2][2], fb0[2][2], fa1[2][2], fb1[2][2];
-    auto frags = [&](hw_f16x8 (&fa)[2][2], hw_f16x8 (&fb)[2][2], int b, int ks) {
+    f16x8 fa0[2][2], fb0[2][2], fa1[2][2], fb1[2][2];
+    auto frags = [&](f16x8 (&fa)[2][2], f16x8 (&fb)[2][2], int b, int ks) {
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl)
-                fa[mb][pl] = *reinterpret_cast<const hw_f16x8 *>(sA + b * kWSzA + fragA + mb * 32 * kWRow +
+                fa[mb][pl] = *reinterpret_cast<const f16x8 *>(sA + b * kWSzA + fragA + mb * 32 * kWRow +
                                                                  16 * ((4 * ks + 2 * pl + fh) ^ fsw));
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl)
-                fb[nb][pl] = *reinterpret_cast<const hw_f16x8 *>(sB + b * kWSzB + fragB + nb * 32 * kWRow +
+                fb[nb][pl] = *reinterpret_cast<const f16x8 *>(sB + b * kWSzB + fragB + nb * 32 * kWRow +
                                                                  16 * ((4 * ks + 2 * pl + fh) ^ fsw));
     };
-    auto mma = [&](const hw_f16x8 (&fa)[2][2], const hw_f16x8 (&fb)[2][2]) {
+    auto mma = [&](const f16x8 (&fa)[2][2], const f16x8 (&fb)[2][2]) {
         constexpr int pa[3] = {1, 0, 0}, pb[3] = {0, 1, 0};       // smallest terms first (as k_fwd_h2)
 #pragma unroll
         for (int t = 0; t < 3; ++t)
@@ -296,30 +289,24 @@ k_fwd_h2w(FwdParams p) {
     }
 }
 
-static inline bool hw_al16(const void *q) { return ((uintptr_t)q & 15) == 0; }
-static inline int hw_env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
 // eligible: one K segment, pre-split weights, K % 32 == 0, no split reduction, enough row tiles to give
 // every CU one (a 128 x 256 tile is a whole CU's work: small N stays with the 64/128 x 128 kernel)
 bool fwd_h2w_launch(const FwdParams &p, hipStream_t hs) {
-    static const int wide = hw_env_int("DC_H2_WIDE", 1);
+    static const int wide = env_int("DC_H2_WIDE", 1);
     if (!p.h2.a_rowmax || !p.h2.b_rowmax || !p.h2.b_presplit || p.nseg != 1) return false;
     if (!wide && p.grp.n < 1 && !p.x2) return false;
     const int64_t ks = p.ksplit > 1 ? p.ksplit : 1;
     if (ks > 1 && (!p.kpartial || p.bias || p.relu || p.exp_lse)) return false;
     if (p.Fi % kWBK != 0 || p.Fi < kWBK) return false;
     if (p.x[0].ld * kWBM >= ((int64_t)1 << 30) || p.Fi * kWBN >= ((int64_t)1 << 30)) return false;
-    if (!hw_al16(p.x[0].p) || !hw_al16(p.w[0].p) || p.x[0].ld % 4 != 0) return false;
+    if (!al16(p.x[0].p) || !al16(p.w[0].p) || p.x[0].ld % 4 != 0) return false;
     const int64_t tiles = ((p.N + kWBM - 1) / kWBM) * ((p.Fo + kWBN - 1) / kWBN);
-    static const int min_tiles = hw_env_int("DC_H2_WIDE_MIN_TILES", 128);
+    static const int min_tiles = env_int("DC_H2_WIDE_MIN_TILES", 128);
     if ((tiles * ks < min_tiles && p.grp.n < 1 && !p.x2) || tiles * ks >= (int64_t)INT32_MAX) return false;
     if (fwd_h2d_launch(p, hs)) return true;            // both operands by LDS-DMA, waves split by role (dc_dense_h2d.hip)
     const dim3 gd((unsigned)(tiles * ks)), bd(512);
     if (p.x2) {
-        if (!p.x2_coef || ks > 1 || !hw_al16(p.x2)) return false;
+        if (!p.x2_coef || ks > 1 || !al16(p.x2)) return false;
         if (p.N % kWBM == 0 && p.Fo % kWBN == 0)
             DC_LAUNCH((k_fwd_h2w<true, true>), gd, bd, 0, hs, p);
         else

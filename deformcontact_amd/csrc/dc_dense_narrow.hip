@@ -33,10 +33,6 @@
 
 namespace dc {
 
-using nb_bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using nb_bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using nb_f32x4 = __attribute__((ext_vector_type(4))) float;
-
 struct NarrowParams {
     const float *x;                 // hop slab [N, ld], Kp valid (zero-padded) columns
     int64_t ld;
@@ -50,20 +46,9 @@ struct NarrowParams {
 
 constexpr int kNarrowFo = 256;
 
-// this wave's LDS operations have completed, then the workgroup meets.  NOT __syncthreads(): its fence waits for vmcnt(0) -
-// for the next tile's rows (issued one tile ahead on purpose) and for the previous tile's 64 KB of row stores - which put two
-// memory round trips per tile on the critical path (30 us per launch instead of 12)
-__device__ __forceinline__ void nb_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-__device__ __forceinline__ void nb_split1(float x, __bf16 &hi, __bf16 &mid, __bf16 &lo) {
-    hi = (__bf16)x;
-    const float r = x - (float)hi;        // exact
-    mid = (__bf16)r;
-    const float r2 = r - (float)mid;      // exact
-    lo = (__bf16)r2;
-}
+// The two barriers per tile are lds_barrier(), NOT __syncthreads(): its fence waits for vmcnt(0) - for the next tile's rows
+// (issued one tile ahead on purpose) and for the previous tile's 64 KB of row stores - which put two memory round trips per
+// tile on the critical path (30 us per launch instead of 12)
 
 // KS: k-steps of 16 (Kp = 16 KS); MB: 32-row blocks per tile
 template <int KS, int MB>
@@ -83,7 +68,7 @@ k_fwd_narrow(NarrowParams p) {
     const int c = lane & 31, h = lane >> 5;
 
     // ---- x tile staging: piece q = threadIdx.x + 256 j of the tile = float4 c4 of row r ----
-    nb_f32x4 xv[NV];
+    f32x4 xv[NV];
     auto load_tile = [&](int t) {
         const int64_t row0 = (int64_t)t * TR;
 #pragma unroll
@@ -93,8 +78,8 @@ k_fwd_narrow(NarrowParams p) {
             const int r = q / PPR, c4 = q - r * PPR;
             int64_t row = row0 + r;
             row = row < p.N ? row : p.N - 1;
-            if (DC_NARROW_ABL & 8) xv[j] = nb_f32x4{(float)row, 1.f, 2.f, 3.f};
-            else xv[j] = *reinterpret_cast<const nb_f32x4 *>(p.x + row * p.ld + 4 * c4);
+            if (DC_NARROW_ABL & 8) xv[j] = f32x4{(float)row, 1.f, 2.f, 3.f};
+            else xv[j] = *reinterpret_cast<const f32x4 *>(p.x + row * p.ld + 4 * c4);
         }
     };
     int t = blockIdx.x;
@@ -112,13 +97,13 @@ k_fwd_narrow(NarrowParams p) {
         float *wi = reinterpret_cast<float *>(lds);
         const int width = p.nseg * p.fi, per4 = kNarrowFo * p.fi / 4;         // float4 pieces per segment (256 fi / 4)
         constexpr int MAXQ = 8;                                              // fi <= 32
-        nb_f32x4 wv[kMaxSeg][MAXQ];
+        f32x4 wv[kMaxSeg][MAXQ];
 #pragma unroll
         for (int s = 0; s < kMaxSeg; ++s)
 #pragma unroll
             for (int j = 0; j < MAXQ; ++j) {
                 const int q = (int)threadIdx.x + 256 * j;
-                if (!(DC_NARROW_ABL & 2) && s < p.nseg && q < per4) wv[s][j] = *reinterpret_cast<const nb_f32x4 *>(p.w[s] + 4 * q);
+                if (!(DC_NARROW_ABL & 2) && s < p.nseg && q < per4) wv[s][j] = *reinterpret_cast<const f32x4 *>(p.w[s] + 4 * q);
             }
 #pragma unroll
         for (int s = 0; s < kMaxSeg; ++s)
@@ -141,18 +126,18 @@ k_fwd_narrow(NarrowParams p) {
         }
     }
     __syncthreads();
-    nb_bf16x8 fb[2][KS][3];
+    bf16x8 fb[2][KS][3];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
         const float *wr = reinterpret_cast<const float *>(lds) + (64 * wid + 32 * nb + c) * WROW + 8 * h;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const nb_f32x4 v0 = *reinterpret_cast<const nb_f32x4 *>(wr + 16 * ks);
-            const nb_f32x4 v1 = *reinterpret_cast<const nb_f32x4 *>(wr + 16 * ks + 4);
+            const f32x4 v0 = *reinterpret_cast<const f32x4 *>(wr + 16 * ks);
+            const f32x4 v1 = *reinterpret_cast<const f32x4 *>(wr + 16 * ks + 4);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 __bf16 hi, mid, lo;
-                nb_split1(j < 4 ? v0[j] : v1[j - 4], hi, mid, lo);
+                split1(j < 4 ? v0[j] : v1[j - 4], hi, mid, lo);
                 fb[nb][ks][0][j] = hi, fb[nb][ks][1][j] = mid, fb[nb][ks][2][j] = lo;
             }
         }
@@ -169,18 +154,18 @@ k_fwd_narrow(NarrowParams p) {
             const int q = (int)threadIdx.x + 256 * j;
             if (TP % 256 != 0 && q >= TP) continue;
             const int r = q / PPR, c4 = q - r * PPR;
-            nb_bf16x4 hi, mid, lo;
+            bf16x4 hi, mid, lo;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 __bf16 a, b, d;
-                nb_split1(xv[j][i], a, b, d);
+                split1(xv[j][i], a, b, d);
                 hi[i] = a, mid[i] = b, lo[i] = d;
             }
             // k = 4 c4 .. + 3: k-step c4 / 4, half (c4 & 3) / 2, position 4 (c4 & 1) inside the half's 8
             char *dst = sA + r * SROWA + (c4 >> 2) * 96 + ((c4 >> 1) & 1) * 16 + (c4 & 1) * 8;
-            *reinterpret_cast<nb_bf16x4 *>(dst) = hi;
-            *reinterpret_cast<nb_bf16x4 *>(dst + 32) = mid;
-            *reinterpret_cast<nb_bf16x4 *>(dst + 64) = lo;
+            *reinterpret_cast<bf16x4 *>(dst) = hi;
+            *reinterpret_cast<bf16x4 *>(dst + 32) = mid;
+            *reinterpret_cast<bf16x4 *>(dst + 64) = lo;
         }
     };
 
@@ -189,8 +174,8 @@ k_fwd_narrow(NarrowParams p) {
 #pragma unroll 4
         for (int r = wid; r < TR; r += 4) {
             const int64_t row = row0 + r;
-            const nb_f32x4 v = *reinterpret_cast<const nb_f32x4 *>(so + r * 256 + 4 * lane);
-            if (row < p.N && (!(DC_NARROW_ABL & 4) || v[0] == 12345.678f)) *reinterpret_cast<nb_f32x4 *>(p.out + row * p.ldo + 4 * lane) = v;
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(so + r * 256 + 4 * lane);
+            if (row < p.N && (!(DC_NARROW_ABL & 4) || v[0] == 12345.678f)) *reinterpret_cast<f32x4 *>(p.out + row * p.ldo + 4 * lane) = v;
         }
     };
     // Order inside an iteration (vector-memory operations retire in order, and hipcc's wait before the first use of the staged
@@ -203,7 +188,7 @@ k_fwd_narrow(NarrowParams p) {
         if (!(DC_NARROW_ABL & 8)) store_tile();         // (every wave is past the MFMAs of the previous tile: barrier B)
         if (prev_row0 >= 0) store_rows(prev_row0);
         if (t + (int)gridDim.x < p.ntiles) load_tile(t + gridDim.x);
-        nb_lds_barrier();                               // A: the plane image is complete; the staging image has been read
+        lds_barrier();                               // A: the plane image is complete; the staging image has been read
         f32x16 acc[MB][2];
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
@@ -215,12 +200,12 @@ k_fwd_narrow(NarrowParams p) {
         constexpr int pa6[6] = {LO, HI, MID, MID, HI, HI}, pb6[6] = {HI, LO, MID, HI, MID, HI};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            nb_bf16x8 fa[MB][3];
+            bf16x8 fa[MB][3];
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    fa[mb][pl] = *reinterpret_cast<const nb_bf16x8 *>(sA + (mb * 32 + c) * SROWA + ks * 96 + pl * 32 + h * 16);
+                    fa[mb][pl] = *reinterpret_cast<const bf16x8 *>(sA + (mb * 32 + c) * SROWA + ks * 96 + pl * 32 + h * 16);
 #pragma unroll
             for (int tt = 0; tt < 6; ++tt)
 #pragma unroll
@@ -244,7 +229,7 @@ k_fwd_narrow(NarrowParams p) {
                     if (!(DC_NARROW_ABL & 16) || r == 0)
                         so[(mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 256 + 64 * wid + 32 * nb + c] = v;
                 }
-        nb_lds_barrier();                               // B: image complete; every wave has read its plane fragments
+        lds_barrier();                               // B: image complete; every wave has read its plane fragments
         prev_row0 = row0;
     }
     if (prev_row0 >= 0) store_rows(prev_row0);

@@ -28,9 +28,6 @@
 
 namespace dc {
 
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
 constexpr int kPlane = 32;                // bytes per plane inside a row (16 bf16)
 
 // NP = number of bf16 MFMA products per tile: 6 = fp32-accurate (hi, mid, lo planes),
@@ -50,27 +47,6 @@ template <int NP> struct Planes {
     static constexpr int NPROD = NP == 2 ? 3 : NP;
     static constexpr int SROW = P * kPlane + 16;     // 112 / 80 / 48 B: conflict-free b128 reads
 };
-
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
-__device__ __forceinline__ void split4_h2(const float4 &v, f16x4 &h, f16x4 &l) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const _Float16 a = (_Float16)x[i];
-        h[i] = a;
-        l[i] = (_Float16)(x[i] - (float)a);          // remainder is exact in fp32
-    }
-}
-
-__device__ __forceinline__ void split1(float x, __bf16 &hi, __bf16 &mid, __bf16 &lo) {
-    hi = (__bf16)x;
-    const float r = x - (float)hi;        // exact
-    mid = (__bf16)r;
-    const float r2 = r - (float)mid;      // exact
-    lo = (__bf16)r2;
-}
 
 __device__ __forceinline__ void split4(const float4 &v, bf16x4 &hi, bf16x4 &mid, bf16x4 &lo) {
     __bf16 h, m, l;
@@ -432,23 +408,6 @@ struct SplitOpRC {
     }
 };
 
-using s16x4 = __attribute__((ext_vector_type(4))) short;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// one MFMA operand (8 consecutive k for column m0 + (lane & 31)) from a [k][m] plane image
-template <int ROWB>
-__device__ __forceinline__ bf16x8 tr_operand(const char *plane, int m0) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-    const int h = g >> 1;
-    const char *a = plane + (8 * h + q) * ROWB + (m0 + 16 * (g & 1) + 4 * pp) * 2;
-    const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(uintptr_t)(a));
-    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (lds_s16x4 *)(uintptr_t)(a + 4 * ROWB));
-    union { s16x4 s[2]; bf16x8 b; } u;
-    u.s[0] = lo4, u.s[1] = hi4;
-    return u.b;
-}
-
 template <int MB, bool MASK, int NP>
 __global__ void __launch_bounds__(256)
 k_dw_split(DwParams p) {
@@ -640,7 +599,6 @@ k_dw_h2w(DwParams p) {
     }
     const float *baseg = p.g.p + n_beg * ldg + o0;                        // wave-uniform running bases
     const float *basex = p.x[s].p + n_beg * ldx;
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
     f32x4 vg0[2], vg1[2], vx0[4], vx1[4];
     f32x4 vc0[2], vc1[2];                                                 // (CORR) pieces of the correction operand
     float cc0[2], cc1[2];                                                 //        and their rows' coefficients
@@ -818,7 +776,6 @@ void transpose_weights_launch(const float *const *ws, int nseg, int64_t Fo, int6
     DC_LAUNCH(k_transpose_w, dim3((unsigned)tiles), dim3(256), 0, hs, t);
 }
 
-static inline bool al16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
 bool fwd_split_launch(const FwdParams &p, int mb, int np, hipStream_t hs) {
     if (np != 6 && np != 3 && np != 1 && np != 2) return false;

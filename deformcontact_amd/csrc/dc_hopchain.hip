@@ -59,19 +59,11 @@ struct ChainParams {
     int32_t node_ptr[kChainGraphs + 1];
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float chain_absmax(const float4 &v) {
     return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
 }
-// this wave's LDS operations have completed (reads returned, writes landed), then the workgroup meets: no vmcnt wait -
-// the block stores of a hop keep draining while the next hop computes (__syncthreads() would wait for them)
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // LDS through plain 32-bit byte addresses (base + offsets folded by hand: one v_lshl_add_u32 per neighbour piece)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 lds_read4(unsigned addr) {
     const f32x4 v = *(const __attribute__((address_space(3))) f32x4 *)(uintptr_t)addr;
     return make_float4(v.x, v.y, v.z, v.w);
@@ -254,9 +246,8 @@ k_hop_chain(ChainParams p) {
         for (int s = 0; s < STEPS; ++s) {
             const int row = rwave + RPW * s + grp;
             if (row < nn && !(DC_CHAIN_ABL & 8))
-                __builtin_amdgcn_global_load_lds(
-                    (const void __attribute__((address_space(1))) *)(src + (int64_t)row * p.ld),
-                    (void __attribute__((address_space(3))) *)(smem + (rwave + RPW * s) * RB), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + (int64_t)row * p.ld), DC_DMA_DST(smem + (rwave + RPW * s) * RB),
+                                                 16, 0, 0);
         }
     }
     if (threadIdx.x < LPR) *reinterpret_cast<float4 *>(smem + zoff + 16 * threadIdx.x) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -269,7 +260,7 @@ k_hop_chain(ChainParams p) {
     const __amdgpu_buffer_rsrc_t rw =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W ? p.w : reinterpret_cast<const float *>(p.other)), 0,
                                           p.cap * 4, 0x00020000);
-    __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0): the slice has landed (a wait hipcc can see:
+    DC_WAITVM(0);                          // vmcnt(0): the slice has landed (a wait hipcc can see:
     lds_barrier();                                               // behind an asm wait it drains vmcnt before every ds_read)
 
     // row maxima: every lane keeps the running maximum of ITS four columns of each of its rows; the lanes of a row piece
@@ -283,7 +274,7 @@ k_hop_chain(ChainParams p) {
             pm[s] = chain_absmax(*reinterpret_cast<const float4 *>(smem + (rwave + RPW * s + grp) * RB + 16 * sub));
     }
 
-    const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
+    const unsigned sbase = lds_addr(smem);
     const unsigned lbase = sbase + 16u * sub - ((DC_CHAIN_ABL & 128) ? 0u : (unsigned)n0 * (unsigned)RB);   // LDS address of a neighbour's piece: id * RB + lbase
     const unsigned zsub = sbase + zoff + 16u * sub;
     const LdsWindow win{sbase + 16u * sub, (unsigned)nn * (unsigned)RB};
@@ -403,15 +394,13 @@ k_hop_chain_gcn(ChainParams p) {
                     *reinterpret_cast<const float4 *>(src + (int64_t)(r0 + grp) * p.ld);
 #else
             if (r0 + grp < nn && !(DC_CHAIN_ABL & 8))
-                __builtin_amdgcn_global_load_lds(
-                    (const void __attribute__((address_space(1))) *)(src + (int64_t)(r0 + grp) * p.ld),
-                    (void __attribute__((address_space(3))) *)(smem + r0 * 128), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + (int64_t)(r0 + grp) * p.ld), DC_DMA_DST(smem + r0 * 128), 16, 0, 0);
 #endif
         }
 #ifdef DC_CHAIN_DMA_READBACK
         // diagnostic build: behind its own vmcnt(0) every DMA wave reads back the last piece it brought in, before the
         // barrier releases the other waves' reads
-        __builtin_amdgcn_s_waitcnt(0x0F70);
+        DC_WAITVM(0);
         {
             const int r_last = (wid - 8) * 16 * STEPS + 8 * (2 * STEPS - 1);
             const float4 v = *reinterpret_cast<const float4 *>(smem + r_last * 128 + 16 * lane);
@@ -441,7 +430,7 @@ k_hop_chain_gcn(ChainParams p) {
                 make_uint4(l[0] | l[1] << 16, l[2] | l[3] << 16, l[4] | l[5] << 16, l[6] | l[7] << 16);
         }
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0): slice and tables have landed
+    DC_WAITVM(0);                          // vmcnt(0): slice and tables have landed
     lds_barrier();
 
     const bool want_rm = p.rowmax != nullptr;
@@ -452,7 +441,7 @@ k_hop_chain_gcn(ChainParams p) {
         if (s < STEPS && want_rm && (p.rm_mode & 1))
             pm[s] = chain_absmax(*reinterpret_cast<const float4 *>(smem + (rwave + 8 * s + grp) * 128 + 16 * sub));
     }
-    const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
+    const unsigned sbase = lds_addr(smem);
     const unsigned lbase = sbase + 16u * sub, dbase = sbase + kDis;
     const unsigned gbase = lbase - (unsigned)n0 * 128u, zsub = lbase + R * 128u;    // global-id addressing of the tail path
     const LdsWindow win{lbase, (unsigned)nn * 128u};

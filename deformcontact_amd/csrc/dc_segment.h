@@ -105,7 +105,6 @@ __device__ __forceinline__ bool seg_row(int lg, int64_t rows, int64_t &row, int 
 }
 
 // ---- host-side checks of the entries ------------------------------------------------------------------------------------
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 // rows x width, and rows x heads x channels per head: what the kernels' int arithmetic holds
 inline bool sizes_ok(int64_t rows, int64_t F) { return rows < (int64_t)INT32_MAX / 4 && F < (1 << 24); }
 inline bool sizes_ok(int64_t N, int64_t H, int64_t C) {

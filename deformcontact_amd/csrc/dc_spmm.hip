@@ -265,12 +265,6 @@ static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 // L lanes share one row, 8 columns (one 16-byte load) per lane and step: F = 256 is 32 lanes,
 // two destination rows per wave.
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // quiet NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 
 struct Bf16x8 { uint4 q; };
 __device__ __forceinline__ void unpack8(const uint4 &q, float (&v)[8]) {

@@ -46,6 +46,38 @@ def test_abi_argument_errors_without_gpu():
     assert rc == -1 and b"key_row" in L.dc_last_error()
 
 
+def test_operand_prep_entries_reject_bad_arguments_without_gpu():
+    """The entries that prepare the operands of the fp16x2 dense blocks (row maxima, masked gradient, weight images,
+    weight transposes) return DC_EINVAL with their own message before any HIP call."""
+    L = _lib.lib()
+    one = (ctypes.c_void_p * 1)(None)                       # a weight list whose only segment is null
+    cases = [
+        (lambda: L.dc_rowabsmax_f32(None, 4, 2, 8, None, None), b"dc_rowabsmax_f32: bad sizes"),          # ld < F
+        (lambda: L.dc_rowabsmax_f32(None, 8, 2, 8, None, None), b"dc_rowabsmax_f32: null pointer"),
+        (lambda: L.dc_tag_weight_rowmax(None, 1, 4, 4, None, None), b"dc_tag_weight_rowmax: bad arguments"),
+        (lambda: L.dc_tag_weight_rowmax(one, 9, 4, 4, 16, None), b"dc_tag_weight_rowmax: bad arguments"),  # nseg > 4
+        (lambda: L.dc_tag_weight_rowmax(one, 1, 4, 4, 16, None), b"dc_tag_weight_rowmax: null segment 0"),
+        (lambda: L.dc_tag_mask_grad(None, 4, None, 0, None, 8, 2, 8, None, None, None), b"dc_tag_mask_grad: bad sizes"),
+        (lambda: L.dc_tag_mask_grad(None, 8, None, 0, None, 8, 2, 8, None, None, None),
+         b"dc_tag_mask_grad: null pointer"),
+        (lambda: L.dc_tag_weight_prep(None, 1, 16, 16, None, None, None, None, None),
+         b"dc_tag_weight_prep: bad arguments"),
+        (lambda: L.dc_tag_weight_prep(one, 1, 16, 16, 16, None, 16, None, None),
+         b"dc_tag_weight_prep: wt_image and wt_rowmax go together"),
+        (lambda: L.dc_tag_weight_prep(one, 1, 16, 12, 16, 16, None, None, None),
+         b"dc_tag_weight_prep: images need a reduction extent that is a multiple of 16"),
+        (lambda: L.dc_tag_weight_prep(one, 1, 16, 16, 16, 24, None, None, None),
+         b"dc_tag_weight_prep: images must be 16-byte aligned"),
+        (lambda: L.dc_tag_weight_prep(one, 1, 16, 16, 16, 16, None, None, None), b"dc_tag_weight_prep: null segment 0"),
+        (lambda: L.dc_tag_weight_prep_zero(one, 1, 16, 16, 16, 16, None, None, None, 4, None),
+         b"dc_tag_weight_prep_zero: bad zero buffer"),
+        (lambda: L.dc_tag_transpose_weights(one, 1, 4, 4, None, None), b"dc_tag_transpose_weights: bad arguments"),
+        (lambda: L.dc_tag_transpose_weights(one, 1, 4, 4, 16, None), b"dc_tag_transpose_weights: null segment 0"),
+    ]
+    for call, message in cases:
+        assert call() == -1 and L.dc_last_error() == message, message
+
+
 def test_adjacency_build_plan_rule(monkeypatch):
     """dc_graph_build_plan: which pipeline an edge set of a given size takes (dc_csr.hip: bucket_plan) - host logic."""
     L = _lib.lib()

@@ -1,5 +1,5 @@
-"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` / ``SAGEConv`` / ``GINConv`` / ``GINEConv`` on
-the HIP hop kernels.
+"""``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` / ``SAGEConv`` / ``GINConv`` / ``GINEConv`` /
+``ChebConv`` on the HIP hop kernels.
 
 Drop-in for the PyG classes the reference instantiates at
 ``/root/reference/models/model.py:39-50`` and calls at ``:71,77``.  Parameter
@@ -20,7 +20,8 @@ unchanged:
 * ``SAGEConv``: ``lin_l.weight [out,in]`` with ``lin_l.bias [out]`` when ``bias``, ``lin_r.weight [out,in]`` when
   ``root_weight``, ``lin.weight [in,in]`` and ``lin.bias [in]`` when ``project`` - all ``U(+-1/sqrt(fan_in))``;
 * ``GINConv`` / ``GINEConv``: ``eps [1]`` (a parameter with ``train_eps``, else a buffer), the keys of the user's module
-  under ``nn.``, and for ``GINEConv(edge_dim=D)`` ``lin.weight [in,D]`` and ``lin.bias [in]`` (``U(+-1/sqrt(D))``).
+  under ``nn.``, and for ``GINEConv(edge_dim=D)`` ``lin.weight [in,D]`` and ``lin.bias [in]`` (``U(+-1/sqrt(D))``);
+* ``ChebConv``: ``lins.{0..K-1}.weight [out,in]`` (glorot, no per-lin bias), ``bias [out]`` (zeros).
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -205,11 +206,13 @@ class _ReluConv(_ConvBase):
         return self.heads * self.out_channels if self.concat else self.out_channels
 
     def _dispatch(self, x: Tensor, edge_index: Tensor, relu: bool, next_conv, width: int, empty_none: bool = False,
-                  **extra: Optional[Tensor]) -> Tensor:
+                  layer=None, **extra: Optional[Tensor]) -> Tensor:
         """``self._layer(g, x, relu, *extra)`` now - or, for the plain PyG call, as a deferred result of ``width``
         columns on the branch's stream.  ``extra``: further tensors of the call (``edge_attr=...`` or None), which must
         be on ``x``'s device, are guarded with ``x`` and make the result want a gradient when they do.  ``empty_none``:
-        no node -> no adjacency is built and ``g`` is None."""
+        no node -> no adjacency is built and ``g`` is None.  ``layer``: what runs in place of ``self._layer`` (same
+        arguments) - a call that carries arguments which are no tensors binds them into it."""
+        layer = layer if layer is not None else self._layer
         x = resolve(x)
         _check_inputs(x, edge_index, self.in_channels)
         for name, t in extra.items():
@@ -225,9 +228,9 @@ class _ReluConv(_ConvBase):
             side = _branch_stream(self, x)
             wanted = _grad_wanted(x, self) or (torch.is_grad_enabled()
                                                and any(t is not None and t.requires_grad for t in extra))
-            return deferred(lambda act: _on_branch(side, lambda: self._layer(graph(), x, act, *extra)),
+            return deferred(lambda act: _on_branch(side, lambda: layer(graph(), x, act, *extra)),
                             x.size(0), width, x, wanted).guard(x, edge_index, *extra, *self.parameters())
-        return self._layer(graph(), x, relu, *extra)
+        return layer(graph(), x, relu, *extra)
 
 
 class TAGConv(_ReluConv):
@@ -630,6 +633,76 @@ class SAGEConv(_ReluConv):
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, aggr={self.aggr}" + (", normalize=True" if self.normalize else "")
                 + ("" if self.root_weight else ", root_weight=False") + (", project=True" if self.project else ""))
+
+
+class ChebConv(_ReluConv):
+    """PyG 2.5.2 ``ChebConv`` (Chebyshev spectral convolution): ``out = sum_k lins[k](Tx_k) + bias`` with ``Tx_0 = x``,
+    ``Tx_1 = L^ x``, ``Tx_k = 2 L^ Tx_{k-1} - Tx_{k-2}`` and ``L^ = 2 L / lambda_max - I`` the scaled Laplacian of
+    ``get_laplacian``: self loops in ``edge_index`` are DROPPED and none is added, duplicates count, the degree is the
+    OUT-degree over what remains (``deg[j]`` = edges with source j), the weight of an edge j -> i is
+    ``-deg_j^-1/2 deg_i^-1/2`` (``"sym"``, ``deg = 0 -> 0``) or ``-1 / deg_j`` (``"rw"``), and every node - an isolated one
+    too - has the diagonal term ``2 / lambda_max - 1``.  ``lambda_max``: None (2.0, the largest value PyG's default can
+    take) or a Python number > 0.  ``K = 1`` is a plain linear layer and builds no adjacency.  The basis is one autograd
+    node on the kernels of dc_cheb.hip (``ops.cheb_basis``), the K linears ONE product of the dense block over it.
+    ``batch`` is accepted and ignored (PyG uses it for per-graph ``lambda_max`` only).  Not supported, each a worded
+    error: ``edge_weight`` other than None; ``normalization=None``; a tensor ``lambda_max`` (per-graph values included)
+    and ``lambda_max <= 0``; bipartite input; bf16-stored input."""
+
+    # the edge set as given: the loops are dropped by their weight, the normalisation is the layer's own (dc_cheb_norm)
+    _self_loops, _gcn_norm = False, False
+
+    def __init__(self, in_channels: int, out_channels: int, K: int, normalization: Optional[str] = "sym",
+                 bias: bool = True):
+        super().__init__()
+        if not isinstance(in_channels, int):
+            raise TypeError("ChebConv: bipartite input (a pair of in_channels) is not supported")
+        if not isinstance(K, int) or isinstance(K, bool) or K < 1:
+            raise ValueError(f"ChebConv: K must be an int >= 1, got {K!r}")
+        if normalization is None:
+            raise NotImplementedError("ChebConv: normalization=None (the unnormalised Laplacian, whose lambda_max PyG "
+                                      "does not default) is not supported; use 'sym' or 'rw'")
+        if normalization not in ops.CHEB_MODES:
+            raise ValueError(f"ChebConv: normalization must be 'sym' or 'rw', got {normalization!r}")
+        self.in_channels, self.out_channels, self.K, self.normalization = in_channels, out_channels, K, normalization
+        self.lins = nn.ModuleList([_Lin(in_channels, out_channels, initializer="glorot") for _ in range(K)])
+        self._init_bias(out_channels, bias)
+
+    def reset_parameters(self):
+        for lin in self.lins:
+            lin.reset_parameters()
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_weight=None, batch=None, lambda_max=None, *,
+                relu: bool = False, next_conv=None) -> Tensor:
+        """``conv(x, edge_index, edge_weight=None, batch=None, lambda_max=None)`` in PyG's positional order;
+        ``relu=True`` fuses the ReLU that follows into the dense block's epilogue, and a plain call returns the deferred
+        result of the other layers."""
+        if edge_weight is not None:
+            raise NotImplementedError("ChebConv: edge_weight is not supported (the Laplacian is built from the edge "
+                                      "set alone); pass None")
+        lam = ops.cheb_lambda(lambda_max, "ChebConv")
+        if isinstance(x, (tuple, list)):
+            raise TypeError("ChebConv: bipartite input (x_src, x_dst) is not supported")
+        x = resolve(x)
+        if isinstance(x, Tensor) and x.dtype == torch.bfloat16:
+            raise NotImplementedError("ChebConv: bf16-stored input is not supported; pass float32")
+
+        def layer(g, x, act):
+            return self._layer(g, x, act, lam)
+        return self._dispatch(x, edge_index, relu, next_conv, self.out_channels, empty_none=True, layer=layer)
+
+    def graph(self, edge_index: Tensor, num_nodes: int, segments=None) -> Optional[GraphIndex]:
+        # K = 1 is x @ W^T + bias: no adjacency
+        return super().graph(edge_index, num_nodes, segments=segments) if self.K > 1 else None
+
+    def _layer(self, g: Optional[GraphIndex], x: Tensor, relu: bool, lam: float = 2.0) -> Tensor:
+        slab = ops.cheb_basis(g, x, self.K, self.normalization, lam)
+        weight = torch.cat([lin.weight for lin in self.lins], 1) if self.K > 1 else self.lins[0].weight
+        return ops.dense_linear(slab, weight, self.bias, relu=relu)
+
+    def extra_repr(self) -> str:
+        return f"{self.in_channels}, {self.out_channels}, K={self.K}, normalization={self.normalization}"
 
 
 def _reset_module(module: nn.Module) -> None:

@@ -863,6 +863,29 @@ int dc_gine_bwd_e(const int64_t *src, const int64_t *dst, const float *x, int64_
                   const float *gy, int64_t ldgy, float *ge, int64_t ldge, int64_t N, int64_t E, int64_t F,
                   dc_stream_t stream);
 
+/* ---- ChebConv: the scaled Laplacian's weights and one step of the Chebyshev recurrence (dc_cheb.hip) ----
+ * The key_row=1 set (ptr / other = source ids) and the key_row=0 set (ptr_t / other_t = destination ids) are those of an
+ * edge set taken as it is given (no self loop added, duplicates count).  A slot whose two ends coincide is a self loop:
+ * it gets weight 0 and is not counted in a degree.  deg[j] = non-loop slots of the key_row=0 segment of j, the OUT-degree
+ * (PyG get_laplacian scatters on edge_index[0]).  Fixed order, no float atomics, no host read: deterministic, capturable.
+ * Arguments are checked before any HIP call: sizes, leading dimensions, then null pointers, then aliasing; N == 0 returns
+ * DC_OK before the null check.
+ *   dc_cheb_norm : mode 0 (sym): dinv[j] = 1 / sqrt(deg[j]), w = dinv[src] * dinv[dst]; mode 1 (rw): dinv[j] = 1 / deg[j],
+ *                  w = dinv[src]; deg = 0 -> dinv = 0.  wl = (2 * -w) / lam in that order (one fp32 division), 0 for a
+ *                  self loop; written per slot of the key_row=1 set (wl_fwd) and of the key_row=0 set (wl_bwd).  dinv
+ *                  fp32 [N] is an output too (the workspace of the second launch).  lam > 0.  Two launches.
+ *   dc_cheb_hop  : s = 0; for p in [ptr[i], ptr[i+1]) in order s += wl[p] * x[other[p],:] (product and sum rounded
+ *                  separately); t = s + b * x[i,:]; y[i,:] = k * t + c * z[i,:] with k in {1, 2}, c in {-1, 0, +1} (c = 0:
+ *                  z is not read, may be NULL, y = k * t); y2[i,:] = z2[i,:] - x[i,:] when y2 is not NULL.  x, z, y, z2,
+ *                  y2: fp32 row-major views [N, F] with their own leading dimensions (column blocks of a slab).  y may
+ *                  be z and y2 may be z2; neither may be x.  Any F >= 1; 16-byte accesses when F % 4 == 0 and every view
+ *                  in use is 16-byte aligned with a row stride that is a multiple of 4.  One launch. */
+int dc_cheb_norm(const int32_t *ptr, const int32_t *other, const int32_t *ptr_t, const int32_t *other_t, int mode,
+                 float lam, float *dinv, float *wl_fwd, float *wl_bwd, int64_t N, dc_stream_t stream);
+int dc_cheb_hop(const int32_t *ptr, const int32_t *other, const float *wl, const float *x, int64_t ldx, const float *z,
+                int64_t ldz, float *y, int64_t ldy, const float *z2, int64_t ldz2, float *y2, int64_t ldy2, float b,
+                int k, int c, int64_t N, int64_t F, dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

@@ -204,6 +204,15 @@ _SIGNATURES = {
     "dc_cheb_norm": (c_int, [_vp, _vp, _vp, _vp, c_int, c_float, _vp, _vp, _vp, c_int64, _vp]),
     "dc_cheb_hop": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_float,
                             c_int, c_int, c_int64, c_int64, _vp]),
+    "dc_gmm_weights": (c_int, [_vp, c_int64, _vp, _vp, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_gmm_fwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int, c_int, _vp, c_int64, c_int64, c_int64,
+                           c_int64, c_int64, _vp]),
+    "dc_gmm_bwd_h": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, c_int64,
+                             _vp]),
+    "dc_gmm_bwd_w": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
+    "dc_gmm_params_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "dc_gmm_bwd_params": (c_int, [_vp, _vp, _vp, c_int64, _vp, _vp, _vp, c_int64, _vp, _vp, _vp, c_int64, c_int64,
+                                  c_int64, c_int64, _vp]),
 }
 
 

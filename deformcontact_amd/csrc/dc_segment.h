@@ -1,5 +1,5 @@
 // dc_segment.h -- the device and host helpers the segment kernels share (dc_gat*.hip, dc_gatv2.hip, dc_transformer.hip,
-// dc_sage.hip, dc_gine.hip, dc_gnn_epi.hip).  Internal; not for the dense / hop / attention translation units.
+// dc_sage.hip, dc_gine.hip, dc_gmm.hip, dc_gnn_epi.hip).  Internal; not for the dense / hop / attention translation units.
 //
 // These kernels promise: every sum in a fixed order, products and sums rounded separately, no float atomics - two runs
 // give the same bits.  The promise rests on the exact operation order of the helpers below, so each is defined ONCE,
@@ -65,6 +65,16 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 // over aligned groups of T lanes (T a power of two <= 64, a run-time value)
 __device__ __forceinline__ float group_sum(float v, int T) {
+    for (int d = T >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+}
+// the same two sums of double partial sums (dot products that cancel: dc_gmm.hip)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+}
+__device__ __forceinline__ double group_sum(double v, int T) {
     for (int d = T >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
     return v;
 }

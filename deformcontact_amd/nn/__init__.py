@@ -8,8 +8,8 @@ graph construction (``knn``, ``knn_graph``, ``radius``, ``radius_graph``,
 ``deformcontact_amd.neighbors``.
 """
 from ..neighbors import knn_graph, radius, radius_graph  # noqa: F401
-from .conv import (ChebConv, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, SAGEConv, TAGConv, TransformerConv,  # noqa: F401
-                   knn)
+from .conv import (ChebConv, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, GMMConv, SAGEConv, TAGConv,  # noqa: F401
+                   TransformerConv, knn)
 
 __all__ = ["TAGConv", "GCNConv", "GATConv", "GATv2Conv", "TransformerConv", "knn", "knn_graph", "radius", "radius_graph",
-           "SAGEConv", "GINConv", "GINEConv", "ChebConv"]
+           "SAGEConv", "GINConv", "GINEConv", "GMMConv", "ChebConv"]

@@ -1,5 +1,5 @@
 """``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` / ``SAGEConv`` / ``GINConv`` / ``GINEConv`` /
-``ChebConv`` on the HIP hop kernels.
+``ChebConv`` / ``GMMConv`` on the HIP hop kernels.
 
 Drop-in for the PyG classes the reference instantiates at
 ``/root/reference/models/model.py:39-50`` and calls at ``:71,77``.  Parameter
@@ -21,7 +21,9 @@ unchanged:
   ``root_weight``, ``lin.weight [in,in]`` and ``lin.bias [in]`` when ``project`` - all ``U(+-1/sqrt(fan_in))``;
 * ``GINConv`` / ``GINEConv``: ``eps [1]`` (a parameter with ``train_eps``, else a buffer), the keys of the user's module
   under ``nn.``, and for ``GINEConv(edge_dim=D)`` ``lin.weight [in,D]`` and ``lin.bias [in]`` (``U(+-1/sqrt(D))``);
-* ``ChebConv``: ``lins.{0..K-1}.weight [out,in]`` (glorot, no per-lin bias), ``bias [out]`` (zeros).
+* ``ChebConv``: ``lins.{0..K-1}.weight [out,in]`` (glorot, no per-lin bias), ``bias [out]`` (zeros);
+* ``GMMConv``: ``g [in,K*out]``, ``mu`` / ``sigma [K,dim]``, ``root.weight [out,in]`` when ``root_weight`` (all glorot),
+  ``bias [out]`` (zeros).
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -703,6 +705,90 @@ class ChebConv(_ReluConv):
 
     def extra_repr(self) -> str:
         return f"{self.in_channels}, {self.out_channels}, K={self.K}, normalization={self.normalization}"
+
+
+class GMMConv(_ReluConv):
+    """PyG 2.5.2 ``GMMConv`` (MoNet, the Gaussian-mixture mesh convolution) with ``separate_gaussians=False``:
+    ``out_i = aggr_{j->i} sum_k w_k(e_ji) (x_j @ g)[k*M:(k+1)*M] + root(x_i) + bias`` with ``w_k(e) = exp(sum_d -0.5
+    (e_d - mu[k,d])^2 / (1e-15 + sigma[k,d]^2))``, ``e = edge_attr`` the D-dimensional pseudo-coordinates of an edge,
+    ``M = out_channels``, ``K = kernel_size``, ``D = dim``.  The edge set exactly as given: no self loop is removed or
+    added, duplicates count (in the degree of ``"mean"`` too), a node without in-edges aggregates 0.  ``aggr``:
+    ``"mean"`` (PyG's default) or ``"add"``.  Parameters as PyG: ``g [in, K*M]``, ``mu`` / ``sigma [K, D]``,
+    ``root.weight [M, in]`` with ``root_weight``, ``bias [M]`` - glorot, the bias zeros.  ``x @ g`` and the root linear
+    run on the dense block; the aggregation with the root term (and the ReLU of ``relu=True`` where the width allows,
+    ``ops.gmm_relu_ok``) is one autograd node on the kernels of dc_gmm.hip (``ops.gmm_aggregate``), which read ``mu`` and
+    ``sigma`` on the device.  ``1 <= kernel_size <= 64``, ``1 <= dim <= 16``.  Not supported, each
+    a worded error: ``separate_gaussians=True``, bipartite input (a pair of ``in_channels``, a pair ``x``),
+    ``aggr="max"``, bf16-stored input."""
+
+    def __init__(self, in_channels: int, out_channels: int, dim: int, kernel_size: int,
+                 separate_gaussians: bool = False, aggr: str = "mean", root_weight: bool = True, bias: bool = True):
+        super().__init__()
+        if separate_gaussians:
+            raise NotImplementedError("GMMConv: separate_gaussians=True (one mixture per input channel) is not "
+                                      "supported")
+        if not isinstance(in_channels, int):
+            raise NotImplementedError("GMMConv: bipartite input (a pair of in_channels) is not supported")
+        if aggr == "max":
+            raise NotImplementedError("GMMConv: aggr='max' is not supported; use 'mean' or 'add'")
+        if not isinstance(aggr, str) or aggr not in ops.GMM_REDUCES:
+            raise ValueError(f"GMMConv: aggr must be 'mean' or 'add', got {aggr!r}")
+        for name, v, cap in (("kernel_size", kernel_size, ops.GMM_MAX_K), ("dim", dim, ops.GMM_MAX_D)):
+            if not isinstance(v, int) or isinstance(v, bool) or not 1 <= v <= cap:
+                raise ValueError(f"GMMConv: {name} must be an int within 1..{cap}, got {v!r}")
+        self.in_channels, self.out_channels, self.dim, self.kernel_size = in_channels, out_channels, dim, kernel_size
+        self.separate_gaussians, self.root_weight, self.aggr = False, bool(root_weight), aggr
+        self.g = nn.Parameter(torch.empty(in_channels, out_channels * kernel_size))
+        self.mu = nn.Parameter(torch.empty(kernel_size, dim))
+        self.sigma = nn.Parameter(torch.empty(kernel_size, dim))
+        self.root = _Lin(in_channels, out_channels, initializer="glorot") if root_weight else None
+        self._init_bias(out_channels, bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            for p in (self.g, self.mu, self.sigma):
+                a = math.sqrt(6.0 / (p.size(-2) + p.size(-1)))
+                p.uniform_(-a, a)
+            if self.bias is not None:
+                self.bias.zero_()
+        if self.root is not None:
+            self.root.reset_parameters()
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None, relu: bool = False,
+                next_conv=None) -> Tensor:
+        """``conv(x, edge_index, edge_attr)`` as PyG.  ``edge_attr``: float32 ``[E, dim]`` (``[E]`` where ``dim`` is 1)
+        with rows in the order of ``edge_index``, on the device of ``x``.  ``relu=True`` runs the ReLU that follows in
+        the aggregation's epilogue (behind the layer at a width the mask pass does not take), and a plain call returns
+        the deferred result of the other layers."""
+        if isinstance(x, (tuple, list)):
+            raise NotImplementedError("GMMConv: bipartite input (x_src, x_dst) is not supported")
+        x = resolve(x)
+        if isinstance(x, Tensor) and x.dtype == torch.bfloat16:
+            raise NotImplementedError("GMMConv: bf16-stored input is not supported; pass float32")
+        if edge_attr is None:
+            raise ValueError("GMMConv needs edge_attr: conv(x, edge_index, edge_attr)")
+        edge_attr = _check_edge_attr(edge_attr, edge_index, self.dim, width_note=" (dim pseudo-coordinates per edge)")
+        if edge_attr.size(0) > 0 and edge_attr.size(1) > 1 and edge_attr.stride(1) != 1:
+            raise ValueError("edge_attr: innermost dimension must be contiguous")
+        return self._dispatch(x, edge_index, relu, next_conv, self.out_channels, empty_none=True, edge_attr=edge_attr)
+
+    def _layer(self, g: Optional[GraphIndex], x: Tensor, relu: bool, edge_attr: Tensor) -> Tensor:
+        h = ops.dense_linear(x, self.g.t())
+        # the root term with the bias is the gather's addend; a bias without a root term is added behind it
+        base = ops.dense_linear(x, self.root.weight, self.bias) if self.root is not None else None
+        late_bias = self.bias if self.root is None else None
+        fused = relu and late_bias is None and ops.gmm_relu_ok(self.out_channels)
+        out = ops.gmm_aggregate(g, h, edge_attr, self.mu, self.sigma, self.aggr, base, fused)
+        if late_bias is not None:
+            out = out + late_bias
+        return torch.relu(out) if relu and not fused else out
+
+    def extra_repr(self) -> str:
+        return f"{self.in_channels}, {self.out_channels}, dim={self.dim}"
+
+    def __repr__(self) -> str:                                   # (PyG's one line, without the ``root`` child)
+        return f"{self.__class__.__name__}({self.extra_repr()})"
 
 
 def _reset_module(module: nn.Module) -> None:

@@ -886,6 +886,49 @@ int dc_cheb_hop(const int32_t *ptr, const int32_t *other, const float *wl, const
                 int64_t ldz, float *y, int64_t ldy, const float *z2, int64_t ldz2, float *y2, int64_t ldy2, float b,
                 int k, int c, int64_t N, int64_t F, dc_stream_t stream);
 
+/* ---- GMMConv (MoNet): a mixture of K Gaussians over D pseudo-coordinates weights K column blocks (dc_gmm.hip) ----
+ * h fp32 [N, K*M] (column k*M + c: kernel k, channel c), a fp32 [E, D] the pseudo-coordinates and w / gw fp32 [E, K]
+ * (dense) in the order of the INPUT edges; mu / sigma fp32 [K, D] dense DEVICE arrays, read by the kernels (they may
+ * change between two replays of a captured launch).  The key_row=1 set (ptr / other / perm) and the key_row=0 set
+ * (ptr_t / other_t / perm_t) are those of an edge set of E edges taken as it is given, as for GINEConv.  Caps:
+ * 1 <= K <= DC_GMM_MAX_K, 1 <= D <= DC_GMM_MAX_D, E * K < 2^31.  Any M >= 1, any in-degree; 16-byte accesses when
+ * M % 4 == 0 and every pointer and row stride is 16-byte aligned.  Sums in a fixed order, no float atomics, no host
+ * read: deterministic and capturable.  Arguments are checked before any HIP call: sizes, leading dimensions, then null
+ * pointers, then aliasing.  N == 0 (dc_gmm_weights, dc_gmm_bwd_w, dc_gmm_bwd_params: E == 0) returns DC_OK before the
+ * null check and launches nothing.  mean: 0 sums, 1 divides by the in-degree.
+ *   dc_gmm_weights    : e = 0; for d in order e += (-0.5 * (t * t)) / (1e-15 + sigma[k,d]^2), t = a[q,d] - mu[k,d];
+ *                       w[q,k] = exp(e) - float32 throughout, as torch evaluates PyG's expression
+ *   dc_gmm_fwd        : s = 0; for p in [ptr[i], ptr[i+1]) in order, for k in order s += w[perm[p],k] * h[other[p],k*M+c]
+ *                       (product and sum rounded separately); mean: s / float(deg) where deg > 0; + base[i,c] (base
+ *                       NULL: none); relu: max(s, 0).  w is never read for a set without edges.
+ *   dc_gmm_bwd_h      : gh[j,k*M+c] = sum over the edges t out of j, in t order, of w[perm_t[t],k] * gs[other_t[t],c];
+ *                       gs[i,c] = gy[i,c] / float(deg_i) with deg from ptr, the key_row=1 pointer (mean), or gy[i,c]
+ *                       (ptr NULL: add).  Every row of gh is written exactly once.
+ *   dc_gmm_bwd_w      : gw[q,k] = sum_c gs[dst[q],c] * h[src[q],k*M+c] for every input edge q < E - src / dst: the two
+ *                       rows of the int64 edge list the sets were built from; ptr as for dc_gmm_bwd_h; an edge with an
+ *                       endpoint outside [0, N) gets a zero row
+ *   dc_gmm_bwd_params : with t = gw[q,k] * w[q,k] and r = (a[q,d] - mu[k,d]) / (1e-15 + sigma[k,d]^2):
+ *                       gmu[k,d] = sum_q t r, gsigma[k,d] = (sum_q t r r) * sigma[k,d] and, ga not NULL,
+ *                       ga[q,d] = -sum_k t r.  Sums in double (as the dot products of dc_gmm_bwd_w): per chunk of edges into the 8-byte aligned workspace
+ *                       (dc_gmm_params_workspace_bytes), then over the chunks in order.  Two launches, three with ga. */
+#define DC_GMM_MAX_K 64
+#define DC_GMM_MAX_D 16
+int dc_gmm_weights(const float *a, int64_t lda, const float *mu, const float *sigma, float *w, int64_t E, int64_t K,
+                   int64_t D, dc_stream_t stream);
+int dc_gmm_fwd(const int32_t *ptr, const int32_t *other, const int32_t *perm, const float *w, const float *h,
+               int64_t ldh, const float *base, int64_t ldb, int mean, int relu, float *y, int64_t ldy, int64_t N,
+               int64_t E, int64_t K, int64_t M, dc_stream_t stream);
+int dc_gmm_bwd_h(const int32_t *ptr_t, const int32_t *other_t, const int32_t *perm_t, const int32_t *ptr,
+                 const float *w, const float *gy, int64_t ldgy, float *gh, int64_t ldgh, int64_t N, int64_t E,
+                 int64_t K, int64_t M, dc_stream_t stream);
+int dc_gmm_bwd_w(const int64_t *src, const int64_t *dst, const int32_t *ptr, const float *h, int64_t ldh,
+                 const float *gy, int64_t ldgy, float *gw, int64_t N, int64_t E, int64_t K, int64_t M,
+                 dc_stream_t stream);
+int64_t dc_gmm_params_workspace_bytes(int64_t E, int64_t K, int64_t D);
+int dc_gmm_bwd_params(const float *gw, const float *w, const float *a, int64_t lda, const float *mu,
+                      const float *sigma, void *workspace, int64_t workspace_bytes, float *gmu, float *gsigma,
+                      float *ga, int64_t ldga, int64_t E, int64_t K, int64_t D, dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

@@ -213,6 +213,14 @@ _SIGNATURES = {
     "dc_gmm_params_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "dc_gmm_bwd_params": (c_int, [_vp, _vp, _vp, c_int64, _vp, _vp, _vp, c_int64, _vp, _vp, _vp, c_int64, c_int64,
                                   c_int64, c_int64, _vp]),
+    "dc_spline_basis": (c_int, [_vp, c_int64, _vp, _vp, c_int64, _vp, _vp, c_int64, c_int64, _vp]),
+    "dc_spline_fwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int, c_int, _vp, c_int64, c_int64,
+                              c_int64, c_int64, c_int64, c_int64, _vp]),
+    "dc_spline_bwd_h": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64,
+                                c_int64, c_int64, _vp]),
+    "dc_spline_bwd_b": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64,
+                                c_int64, _vp]),
+    "dc_spline_bwd_a": (c_int, [_vp, _vp, c_int64, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
 }
 
 

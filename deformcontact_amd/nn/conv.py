@@ -1,5 +1,5 @@
 """``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` / ``SAGEConv`` / ``GINConv`` / ``GINEConv`` /
-``ChebConv`` / ``GMMConv`` on the HIP hop kernels.
+``ChebConv`` / ``GMMConv`` / ``SplineConv`` on the HIP hop kernels.
 
 Drop-in for the PyG classes the reference instantiates at
 ``/root/reference/models/model.py:39-50`` and calls at ``:71,77``.  Parameter
@@ -23,7 +23,10 @@ unchanged:
   under ``nn.``, and for ``GINEConv(edge_dim=D)`` ``lin.weight [in,D]`` and ``lin.bias [in]`` (``U(+-1/sqrt(D))``);
 * ``ChebConv``: ``lins.{0..K-1}.weight [out,in]`` (glorot, no per-lin bias), ``bias [out]`` (zeros);
 * ``GMMConv``: ``g [in,K*out]``, ``mu`` / ``sigma [K,dim]``, ``root.weight [out,in]`` when ``root_weight`` (all glorot),
-  ``bias [out]`` (zeros).
+  ``bias [out]`` (zeros);
+* ``SplineConv``: ``weight [K,in,out]`` (``U(+-1/sqrt(K*in))``, ``K`` the product of ``kernel_size``), ``lin.weight
+  [out,in]`` when ``root_weight`` (``U(+-1/sqrt(in))``), ``bias [out]`` (zeros), the buffers ``kernel_size [dim]`` int64
+  and ``is_open_spline [dim]`` uint8.
 
 No CPU path: calling a conv with CPU tensors raises.
 """
@@ -788,6 +791,93 @@ class GMMConv(_ReluConv):
         return f"{self.in_channels}, {self.out_channels}, dim={self.dim}"
 
     def __repr__(self) -> str:                                   # (PyG's one line, without the ``root`` child)
+        return f"{self.__class__.__name__}({self.extra_repr()})"
+
+
+class SplineConv(_ReluConv):
+    """PyG 2.5.2 ``SplineConv`` (SplineCNN, the B-spline mesh convolution) with torch-spline-conv's basis and weighting:
+    ``out_i = aggr_{j->i} sum_s b_s(e_ji) (x_j @ weight[wi_s(e_ji)]) + lin(x_i) + bias``, ``e = edge_attr`` the
+    D-dimensional pseudo-coordinates of an edge in [0, 1], ``M = out_channels``, ``D = dim``.  Per dimension an open or
+    closed B-spline of ``degree`` 1..3 with ``kernel_size[d]`` control points: an edge touches ``S = (degree+1)^D`` of
+    the ``K = prod kernel_size`` weight matrices (INTEGRATION.md 1.9 states the basis and the index).  The edge set
+    exactly as given: no self loop is removed or added, duplicates count (in the degree of ``"mean"`` too), a node
+    without in-edges aggregates 0.  ``aggr``: ``"mean"`` (PyG's default) or ``"add"``.  Parameters as PyG: ``weight
+    [K, in, M]``, ``lin.weight [M, in]`` with ``root_weight``, ``bias [M]``, and the buffers ``kernel_size`` /
+    ``is_open_spline``; the kernels use the constructor's Python values, never the buffers.  ``x @ weight[k]`` for all
+    k (one ``[N, K*M]`` product) and the root linear run on the dense block; the aggregation with the root term (and the
+    ReLU of ``relu=True`` where the width allows, ``ops.gmm_relu_ok``) is one autograd node on the kernels of
+    dc_spline.hip (``ops.spline_aggregate``).  Coordinates outside [0, 1] wrap (no out-of-bounds read), NaN propagates.
+    ``1 <= dim <= 4``, ``S <= 64``, ``K <= 1024``.  Not supported, each a worded error: bipartite input (a pair of
+    ``in_channels``, a pair ``x``), lazy ``in_channels``, ``aggr="max"``, bf16-stored input."""
+
+    def __init__(self, in_channels: int, out_channels: int, dim: int, kernel_size, is_open_spline=True, degree: int = 1,
+                 aggr: str = "mean", root_weight: bool = True, bias: bool = True):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise NotImplementedError("SplineConv: bipartite input (a pair of in_channels) is not supported")
+        if not isinstance(in_channels, int) or in_channels <= 0:
+            raise NotImplementedError(f"SplineConv: in_channels must be a positive int (lazy initialisation is not "
+                                      f"supported), got {in_channels!r}")
+        if aggr == "max":
+            raise NotImplementedError("SplineConv: aggr='max' is not supported; use 'mean' or 'add'")
+        if not isinstance(aggr, str) or aggr not in ops.SPLINE_REDUCES:
+            raise ValueError(f"SplineConv: aggr must be 'mean' or 'add', got {aggr!r}")
+        self._geom = ops.spline_geometry(kernel_size, is_open_spline, degree, dim, who="SplineConv")
+        ks, op, _, k, _ = self._geom
+        self.in_channels, self.out_channels, self.dim, self.degree = in_channels, out_channels, dim, degree
+        self.root_weight, self.aggr = bool(root_weight), aggr
+        self.register_buffer("kernel_size", torch.tensor(ks, dtype=torch.long))
+        self.register_buffer("is_open_spline", torch.tensor(op, dtype=torch.uint8))
+        self.weight = nn.Parameter(torch.empty(k, in_channels, out_channels))
+        self.lin = _Lin(in_channels, out_channels) if root_weight else None
+        self._init_bias(out_channels, bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            a = 1.0 / math.sqrt(self.weight.size(0) * self.weight.size(1))
+            self.weight.uniform_(-a, a)
+            if self.bias is not None:
+                self.bias.zero_()
+        if self.lin is not None:
+            self.lin.reset_parameters()
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None, relu: bool = False,
+                next_conv=None) -> Tensor:
+        """``conv(x, edge_index, edge_attr)`` as PyG.  ``edge_attr``: float32 ``[E, dim]`` (``[E]`` where ``dim`` is 1)
+        in [0, 1] with rows in the order of ``edge_index``, on the device of ``x``.  ``relu=True`` runs the ReLU that
+        follows in the aggregation's epilogue (behind the layer at a width the mask pass does not take), and a plain
+        call returns the deferred result of the other layers."""
+        if isinstance(x, (tuple, list)):
+            raise NotImplementedError("SplineConv: bipartite input (x_src, x_dst) is not supported")
+        x = resolve(x)
+        if isinstance(x, Tensor) and x.dtype == torch.bfloat16:
+            raise NotImplementedError("SplineConv: bf16-stored input is not supported; pass float32")
+        if edge_attr is None:
+            raise ValueError("SplineConv needs edge_attr: conv(x, edge_index, edge_attr)")
+        edge_attr = _check_edge_attr(edge_attr, edge_index, self.dim, width_note=" (dim pseudo-coordinates per edge)")
+        if edge_attr.size(0) > 0 and edge_attr.size(1) > 1 and edge_attr.stride(1) != 1:
+            raise ValueError("edge_attr: innermost dimension must be contiguous")
+        return self._dispatch(x, edge_index, relu, next_conv, self.out_channels, empty_none=True, edge_attr=edge_attr)
+
+    def _layer(self, g: Optional[GraphIndex], x: Tensor, relu: bool, edge_attr: Tensor) -> Tensor:
+        ks, op, degree, k, _ = self._geom
+        # [K, in, M] -> [K*M, in]: row k*M + c is column c of weight[k] (a torch copy: autograd carries g_weight)
+        w2 = self.weight.permute(0, 2, 1).reshape(k * self.out_channels, self.in_channels)
+        h = ops.dense_linear(x, w2)
+        # the root term with the bias is the gather's addend; a bias without a root term is added behind it
+        base = ops.dense_linear(x, self.lin.weight, self.bias) if self.lin is not None else None
+        late_bias = self.bias if self.lin is None else None
+        fused = relu and late_bias is None and ops.gmm_relu_ok(self.out_channels)
+        out = ops.spline_aggregate(g, h, edge_attr, ks, op, degree, self.aggr, base, fused)
+        if late_bias is not None:
+            out = out + late_bias
+        return torch.relu(out) if relu and not fused else out
+
+    def extra_repr(self) -> str:
+        return f"{self.in_channels}, {self.out_channels}, dim={self.dim}"
+
+    def __repr__(self) -> str:                                   # (PyG's one line, without the ``lin`` child)
         return f"{self.__class__.__name__}({self.extra_repr()})"
 
 

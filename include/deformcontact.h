@@ -929,6 +929,55 @@ int dc_gmm_bwd_params(const float *gw, const float *w, const float *a, int64_t l
                       const float *sigma, void *workspace, int64_t workspace_bytes, float *gmu, float *gsigma,
                       float *ga, int64_t ldga, int64_t E, int64_t K, int64_t D, dc_stream_t stream);
 
+/* ---- SplineConv (SplineCNN): a B-spline over D pseudo-coordinates picks and weights S of K column blocks (dc_spline.hip) ----
+ * h fp32 [N, K*M] (column k*M + c: weight matrix k, channel c), a fp32 [E, D] the pseudo-coordinates, b / gb fp32 [E, S]
+ * and wi int32 [E, S] (dense) in the order of the INPUT edges, S = (degree+1)^D.  ks (int64 [D], the kernel size per
+ * dimension) and open (int32 [D], non-zero: open spline) are HOST arrays: they and degree are copied into the kernel
+ * arguments, K = prod ks[d].  The key_row=1 set (ptr / other / perm) and the key_row=0 set (ptr_t / other_t / perm_t) are
+ * those of an edge set of E edges taken as it is given, as for GMMConv.  Caps: 1 <= D <= DC_SPLINE_MAX_D, 1 <= degree
+ * <= 3, S <= DC_SPLINE_MAX_S, ks[d] >= 1, K <= DC_SPLINE_MAX_K, E * S < 2^31, N * K * M < 2^31.  Any M >= 1, any
+ * in-degree; 16-byte accesses when M % 4 == 0 and every pointer and row stride is 16-byte aligned.  Sums in a fixed
+ * order, no float atomics, no host read: deterministic and capturable.  Arguments are checked before any HIP call:
+ * sizes, leading dimensions, then null pointers, then ks, then aliasing.  N == 0 (dc_spline_basis, dc_spline_bwd_b,
+ * dc_spline_bwd_a: E == 0) returns DC_OK before the null check and launches nothing.  mean: 0 sums, 1 divides by the
+ * in-degree.
+ *   dc_spline_basis : for slot s, with k = s, wi = 0, off = 1, b = 1, for d in order: k_mod = k % (degree+1), k /= degree+1,
+ *                     v = a[q,d] * float(ks[d] - degree*open[d]), wi += ((floor(v) + k_mod) mod ks[d]) * off, off *= ks[d],
+ *                     b *= B_degree(v - floor(v), k_mod) - float32 throughout; the modulo is the non-negative one of
+ *                     floor(v) clamped to +-2^30 (NaN: 0), so 0 <= wi < K for every a.
+ *                     B_1(f,k) = 1 - f - k + 2fk; B_2 = (f^2/2 - f + 1/2, -f^2 + f + 1/2, f^2/2);
+ *                     B_3 = ((1-f)^3, 3f^3 - 6f^2 + 4, -3f^3 + 3f^2 + 3f + 1, f^3) / 6
+ *   dc_spline_fwd   : acc = 0; for p in [ptr[i], ptr[i+1]) in order: t = 0, for s in order t += b[perm[p],s] *
+ *                     h[other[p], wi[perm[p],s]*M + c] (product and sum rounded separately), then acc += t (the edge's
+ *                     message first, then the sum over the edges); mean: acc / float(deg) where deg > 0; + base[i,c]
+ *                     (base NULL: none); relu: max(acc, 0).  b and wi are never read for a set without edges; wi must
+ *                     hold values in [0, K) (those of dc_spline_basis).
+ *   dc_spline_bwd_h : gh[j,k*M+c] = sum over the edges t out of j, in t order, and the slots s with wi[perm_t[t],s] == k,
+ *                     in s order, of b[perm_t[t],s] * gs[other_t[t],c]; gs[i,c] = gy[i,c] / float(deg_i) with deg from
+ *                     ptr, the key_row=1 pointer (mean), or gy[i,c] (ptr NULL: add).  Every column of every row of gh is
+ *                     written exactly once, zeros included.
+ *   dc_spline_bwd_b : gb[q,s] = sum_c gs[dst[q],c] * h[src[q], wi[q,s]*M + c] for every input edge q < E, formed in
+ *                     double and rounded once - src / dst: the two rows of the int64 edge list the sets were built from;
+ *                     ptr as for dc_spline_bwd_h; an edge with an endpoint outside [0, N) gets a zero row
+ *   dc_spline_bwd_a : ga[q,d] = float(ks[d] - degree*open[d]) * sum_s gb[q,s] * B'(f_d, k_mod_d) * prod_{d' != d}
+ *                     B(f_d', k_mod_d') with the float32 fractions f of dc_spline_basis, formed in double and rounded once */
+#define DC_SPLINE_MAX_D 4
+#define DC_SPLINE_MAX_S 64
+#define DC_SPLINE_MAX_K 1024
+int dc_spline_basis(const float *a, int64_t lda, const int64_t *ks, const int32_t *open, int64_t degree, float *b,
+                    int32_t *wi, int64_t E, int64_t D, dc_stream_t stream);
+int dc_spline_fwd(const int32_t *ptr, const int32_t *other, const int32_t *perm, const float *b, const int32_t *wi,
+                  const float *h, int64_t ldh, const float *base, int64_t ldb, int mean, int relu, float *y,
+                  int64_t ldy, int64_t N, int64_t E, int64_t S, int64_t K, int64_t M, dc_stream_t stream);
+int dc_spline_bwd_h(const int32_t *ptr_t, const int32_t *other_t, const int32_t *perm_t, const int32_t *ptr,
+                    const float *b, const int32_t *wi, const float *gy, int64_t ldgy, float *gh, int64_t ldgh,
+                    int64_t N, int64_t E, int64_t S, int64_t K, int64_t M, dc_stream_t stream);
+int dc_spline_bwd_b(const int64_t *src, const int64_t *dst, const int32_t *ptr, const int32_t *wi, const float *h,
+                    int64_t ldh, const float *gy, int64_t ldgy, float *gb, int64_t N, int64_t E, int64_t S, int64_t K,
+                    int64_t M, dc_stream_t stream);
+int dc_spline_bwd_a(const float *gb, const float *a, int64_t lda, const int64_t *ks, const int32_t *open,
+                    int64_t degree, float *ga, int64_t ldga, int64_t E, int64_t D, dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

@@ -201,6 +201,11 @@ _SIGNATURES = {
                               c_int64, _vp]),
     "dc_gine_bwd_e": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64,
                               c_int64, _vp]),
+    "dc_edge_pair_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
+    "dc_edge_pair_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_edge_reduce_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int, c_int64, c_int64, _vp]),
+    "dc_edge_reduce_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64,
+                                   c_int, c_int64, c_int64, c_int64, _vp]),
     "dc_cheb_norm": (c_int, [_vp, _vp, _vp, _vp, c_int, c_float, _vp, _vp, _vp, c_int64, _vp]),
     "dc_cheb_hop": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_float,
                             c_int, c_int, c_int64, c_int64, _vp]),

@@ -31,25 +31,6 @@ namespace {
 constexpr int kEdgesSg = 8;        // rows in flight per lane: one gathered array per edge (mean, max forward)
 constexpr int kEdgesSgBwd = 4;     // the max backward gathers three arrays per edge
 
-// the count image of the max: Cols / cols_load / cols_store (dc_segment.h) for int32, an absent element reads as 1
-template <int VEC> struct IntsSg { int a[VEC]; };
-template <int VEC>
-__device__ __forceinline__ IntsSg<VEC> sg_load_i(const int32_t *p, bool ok) {
-    IntsSg<VEC> r;
-    if constexpr (VEC == 4) {
-        const int4 v = ok ? *reinterpret_cast<const int4 *>(p) : make_int4(1, 1, 1, 1);
-        r.a[0] = v.x, r.a[1] = v.y, r.a[2] = v.z, r.a[3] = v.w;
-    } else {
-        r.a[0] = ok ? *p : 1;
-    }
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ void sg_store_i(int32_t *p, const int (&v)[VEC]) {
-    if constexpr (VEC == 4) *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
-
 }  // namespace
 
 // ---- mean, forward ---------------------------------------------------------------------------------------------------
@@ -169,7 +150,7 @@ k_sage_max_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ othe
             for (int k = 0; k < VEC; ++k) mx[k] = 0.f;
         }
         cols_store<VEC>(m + row * ldm + c, mx);
-        if (cnt) sg_store_i<VEC>(cnt + row * ldc + c, ct);
+        if (cnt) ints_store<VEC>(cnt + row * ldc + c, ct);
     }
 }
 
@@ -196,13 +177,13 @@ k_sage_max_bwd(const int32_t *__restrict__ ptr_t, const int32_t *__restrict__ ot
             const int n = end - p;
             int64_t s[U];
             Cols<VEC> mv[U], gv[U];
-            IntsSg<VEC> cv[U];
+            Ints<VEC> cv[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = u < n ? other_t[p + u] : row;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 mv[u] = cols_load<VEC>(m + s[u] * ldm + c, u < n);
-                cv[u] = sg_load_i<VEC>(cnt + s[u] * ldc + c, u < n);
+                cv[u] = ints_load<VEC>(cnt + s[u] * ldc + c, u < n);
                 gv[u] = cols_load<VEC>(gm + s[u] * ldgm + c, u < n);
             }
 #pragma unroll

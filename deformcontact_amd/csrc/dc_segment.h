@@ -1,5 +1,5 @@
 // dc_segment.h -- the device and host helpers the segment kernels share (dc_gat*.hip, dc_gatv2.hip, dc_transformer.hip,
-// dc_sage.hip, dc_gine.hip, dc_gmm.hip, dc_gnn_epi.hip).  Internal; not for the dense / hop / attention translation units.
+// dc_sage.hip, dc_gine.hip, dc_edge.hip, dc_gmm.hip, dc_gnn_epi.hip).  Internal; not for the dense / hop / attention translation units.
 //
 // These kernels promise: every sum in a fixed order, products and sums rounded separately, no float atomics - two runs
 // give the same bits.  The promise rests on the exact operation order of the helpers below, so each is defined ONCE,
@@ -54,6 +54,25 @@ __device__ __forceinline__ Cols<VEC> cols_load(const float *p, bool ok) {
 template <int VEC>
 __device__ __forceinline__ void cols_store(float *p, const float (&v)[VEC]) {
     if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *p = v[0];
+}
+
+// the same for an int32 image (the tie counts of a max: dc_sage.hip, dc_edge.hip); an absent element reads as 1
+template <int VEC> struct Ints { int a[VEC]; };
+template <int VEC>
+__device__ __forceinline__ Ints<VEC> ints_load(const int32_t *p, bool ok) {
+    Ints<VEC> r;
+    if constexpr (VEC == 4) {
+        const int4 v = ok ? *reinterpret_cast<const int4 *>(p) : make_int4(1, 1, 1, 1);
+        r.a[0] = v.x, r.a[1] = v.y, r.a[2] = v.z, r.a[3] = v.w;
+    } else {
+        r.a[0] = ok ? *p : 1;
+    }
+    return r;
+}
+template <int VEC>
+__device__ __forceinline__ void ints_store(int32_t *p, const int (&v)[VEC]) {
+    if constexpr (VEC == 4) *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
     else *p = v[0];
 }
 

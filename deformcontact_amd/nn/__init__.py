@@ -8,8 +8,8 @@ graph construction (``knn``, ``knn_graph``, ``radius``, ``radius_graph``,
 ``deformcontact_amd.neighbors``.
 """
 from ..neighbors import knn_graph, radius, radius_graph  # noqa: F401
-from .conv import (ChebConv, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, GMMConv, SAGEConv, SplineConv,  # noqa: F401
+from .conv import (ChebConv, EdgeConv, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, GMMConv, SAGEConv, SplineConv,  # noqa: F401
                    TAGConv, TransformerConv, knn)
 
 __all__ = ["TAGConv", "GCNConv", "GATConv", "GATv2Conv", "TransformerConv", "knn", "knn_graph", "radius", "radius_graph",
-           "SAGEConv", "GINConv", "GINEConv", "SplineConv", "GMMConv", "ChebConv"]
+           "SAGEConv", "GINConv", "GINEConv", "EdgeConv", "SplineConv", "GMMConv", "ChebConv"]

@@ -1,5 +1,5 @@
 """``TAGConv`` / ``GCNConv`` / ``GATConv`` / ``GATv2Conv`` / ``TransformerConv`` / ``SAGEConv`` / ``GINConv`` / ``GINEConv`` /
-``ChebConv`` / ``GMMConv`` / ``SplineConv`` on the HIP hop kernels.
+``EdgeConv`` / ``ChebConv`` / ``GMMConv`` / ``SplineConv`` on the HIP hop kernels.
 
 Drop-in for the PyG classes the reference instantiates at
 ``/root/reference/models/model.py:39-50`` and calls at ``:71,77``.  Parameter
@@ -21,6 +21,7 @@ unchanged:
   ``root_weight``, ``lin.weight [in,in]`` and ``lin.bias [in]`` when ``project`` - all ``U(+-1/sqrt(fan_in))``;
 * ``GINConv`` / ``GINEConv``: ``eps [1]`` (a parameter with ``train_eps``, else a buffer), the keys of the user's module
   under ``nn.``, and for ``GINEConv(edge_dim=D)`` ``lin.weight [in,D]`` and ``lin.bias [in]`` (``U(+-1/sqrt(D))``);
+* ``EdgeConv``: the keys of the user's module under ``nn.`` and nothing else;
 * ``ChebConv``: ``lins.{0..K-1}.weight [out,in]`` (glorot, no per-lin bias), ``bias [out]`` (zeros);
 * ``GMMConv``: ``g [in,K*out]``, ``mu`` / ``sigma [K,dim]``, ``root.weight [out,in]`` when ``root_weight`` (all glorot),
   ``bias [out]`` (zeros);
@@ -998,6 +999,46 @@ class GINEConv(_GinBase):
         if edge_attr.size(0) > 0 and edge_attr.size(1) > 1 and edge_attr.stride(1) != 1:
             raise ValueError("edge_attr: innermost dimension must be contiguous")
         return edge_attr
+
+
+class EdgeConv(_ConvBase):
+    """PyG 2.5.2 ``EdgeConv`` (the layer of DGCNN): ``out_i = aggr_j nn([x_i, x_j - x_i])`` over the incoming edges
+    ``j -> i`` - the edge set exactly as given: no self loop is removed or added, duplicates count, a node without
+    in-edges gets 0.  ``nn`` is any ``torch.nn.Module`` and is called as it is, once, on the ``[E, 2 * in]`` rows of all
+    edges in the order of ``edge_index``; its result must be float32 ``[E, C]``.  ``aggr``: ``"max"`` (default),
+    ``"mean"``, ``"sum"`` or its alias ``"add"``.  The pair rows and the reduction are one autograd node each on the
+    kernels of dc_edge.hip (``ops.edge_pairs``, ``ops.edge_aggregate``): every sum in a fixed order, no float atomics,
+    and the gradient of a maximum goes in equal shares to all edges that attain it.  The
+    layer's result is the reduction's, so there is no ``relu=`` / ``next_conv=`` and no deferred result.  Not
+    supported: bipartite ``(x_src, x_dst)`` input (a ``TypeError``), aggregation lists or modules, bf16-stored input."""
+
+    def __init__(self, nn: nn.Module, aggr: str = "max"):
+        super().__init__()
+        if not isinstance(aggr, str) or aggr not in ("max", "mean", "sum", "add"):
+            raise ValueError(f"EdgeConv: aggr must be 'max', 'mean', 'sum' or 'add', got {aggr!r}")
+        self.nn = nn
+        self.aggr = "sum" if aggr == "add" else aggr
+
+    def reset_parameters(self):
+        _reset_module(self.nn)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        """``conv(x, edge_index)`` as PyG; a deferred ``x`` is resolved."""
+        if isinstance(x, (tuple, list)):
+            raise TypeError("EdgeConv: bipartite (x_src, x_dst) input is not supported; pass one [N, F] tensor")
+        x = resolve(x)
+        _check_inputs(x, edge_index, x.size(1) if x.dim() == 2 else -1)
+        g = self.graph(edge_index, x.size(0)) if x.size(0) else None
+        z = ops.edge_pairs(g, x)
+        m = resolve(self.nn(z))              # (no edge: nn sees the empty [0, 2F] tensor and tells the output's width)
+        if not isinstance(m, Tensor) or m.dim() != 2 or m.dtype != torch.float32 or m.size(0) != z.size(0) \
+                or m.size(1) == 0:
+            got = f"{tuple(m.shape)} {m.dtype}" if isinstance(m, Tensor) else type(m).__name__
+            raise ValueError(f"EdgeConv: nn must return a float32 [E, C >= 1] tensor with E = {z.size(0)} rows, got {got}")
+        return ops.edge_aggregate(g, m, self.aggr)
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}(nn={self.nn})"
 
 
 # ``models/model.py:2`` imports ``knn`` from here (it never calls it): the device search of ``neighbors``

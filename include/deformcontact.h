@@ -863,6 +863,41 @@ int dc_gine_bwd_e(const int64_t *src, const int64_t *dst, const float *x, int64_
                   const float *gy, int64_t ldgy, float *ge, int64_t ldge, int64_t N, int64_t E, int64_t F,
                   dc_stream_t stream);
 
+/* ---- Per-edge primitives of the "module per edge" layers (EdgeConv): pair rows and edge-row reductions (dc_edge.hip) ----
+ * x fp32 [N, F] are the node rows; z [E, 2F], m [E, C] and their gradients are edge rows in the order of the INPUT edges
+ * (row strides ld* >= the width).  src / dst: the two rows of the int64 edge list; the key_row=1 set (ptr / perm = input
+ * edge id of every sorted position) and the key_row=0 set (ptr_t / perm_t) are those of that edge list taken as it is
+ * given - no self loop is added, duplicates count, a row may have no edge.  Any width >= 1 (no cap), any in-degree >= 0;
+ * 16-byte loads when the width % 4 == 0 and every pointer and row stride is 16-byte aligned.  Sums in a fixed order, no
+ * float atomics, no workspace, no host read: deterministic and capturable.  Inputs are taken to be finite.  Arguments
+ * are checked before any HIP call, in the order of the GINE entries: sizes and leading dimensions, then null pointers,
+ * then aliasing.  A zero row count (E for the entries that walk the input edges, N for the others) returns DC_OK
+ * before the null check.  mode: 0 sum, 1 mean, 2 max.
+ *   dc_edge_pair_fwd   : z[q,c] = x[dst[q],c]; z[q,F+c] = x[src[q],c] - x[dst[q],c] (one fp32 subtraction) for every
+ *                        input edge q < E; every row of z is written exactly once; an edge with an endpoint outside
+ *                        [0, N) gets a zero row of 2F
+ *   dc_edge_pair_bwd   : gx[j,c] = the compensated sum of, first, gz[perm[p],c] - gz[perm[p],F+c] (the difference formed
+ *                        first, in fp32) for p in [ptr[j], ptr[j+1]) in order, then gz[perm_t[t],F+c] for t in
+ *                        [ptr_t[j], ptr_t[j+1]) in order; 0 for a node without edges
+ *   dc_edge_reduce_fwd : sum: acc = 0, acc = acc + m[perm[p],c] in p order (plain fp32); mean: that sum / float(ptr[i+1]
+ *                        - ptr[i]), a true division; max: y[i,c] = the maximum, cnt[i,c] (int32) = the number of edges
+ *                        of the row that attain it - cnt is required for mode 2 and must be NULL otherwise; a row
+ *                        without edges gives 0 (cnt 0)
+ *   dc_edge_reduce_bwd : for every input edge q < E, i = dst[q]: sum gm[q,c] = gy[i,c]; mean gm[q,c] = gy[i,c] /
+ *                        float(ptr[i+1] - ptr[i]); max gm[q,c] = (m[q,c] == y[i,c]) ? gy[i,c] / float(cnt[i,c]) : 0 - the
+ *                        gradient of a maximum split EVENLY among all edges that attain it.  ptr is read in mode 1 only,
+ *                        m / y / cnt in mode 2 only (NULL otherwise); every row of gm is written exactly once; an edge
+ *                        with an endpoint outside [0, N) gets a zero row */
+int dc_edge_pair_fwd(const int64_t *src, const int64_t *dst, const float *x, int64_t ldx, float *z, int64_t ldz,
+                     int64_t N, int64_t E, int64_t F, dc_stream_t stream);
+int dc_edge_pair_bwd(const int32_t *ptr, const int32_t *perm, const int32_t *ptr_t, const int32_t *perm_t,
+                     const float *gz, int64_t ldgz, float *gx, int64_t ldgx, int64_t N, int64_t F, dc_stream_t stream);
+int dc_edge_reduce_fwd(const int32_t *ptr, const int32_t *perm, const float *m, int64_t ldm, float *y, int64_t ldy,
+                       int32_t *cnt, int64_t ldc, int mode, int64_t N, int64_t C, dc_stream_t stream);
+int dc_edge_reduce_bwd(const int64_t *src, const int64_t *dst, const int32_t *ptr, const float *m, int64_t ldm,
+                       const float *y, int64_t ldy, const int32_t *cnt, int64_t ldc, const float *gy, int64_t ldgy,
+                       float *gm, int64_t ldgm, int mode, int64_t N, int64_t E, int64_t C, dc_stream_t stream);
+
 /* ---- ChebConv: the scaled Laplacian's weights and one step of the Chebyshev recurrence (dc_cheb.hip) ----
  * The key_row=1 set (ptr / other = source ids) and the key_row=0 set (ptr_t / other_t = destination ids) are those of an
  * edge set taken as it is given (no self loop added, duplicates count).  A slot whose two ends coincide is a self loop:

@@ -226,6 +226,13 @@ _SIGNATURES = {
     "dc_spline_bwd_b": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64,
                                 c_int64, _vp]),
     "dc_spline_bwd_a": (c_int, [_vp, _vp, c_int64, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
+    "dc_fps_resident_points": (c_int64, []),
+    "dc_fps_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "dc_fps": (c_int, [_vp, c_int64, c_int64, _vp, _vp, c_int64, c_int64, _vp, _vp, c_int64, _vp, c_int64, _vp]),
+    "dc_knn_interpolate_fwd": (c_int, [_vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, _vp, c_int, _vp, c_int64, _vp, _vp,
+                                       c_int64, c_int64, c_int64, _vp]),
+    "dc_knn_interpolate_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int, c_int64, c_int64, c_int64,
+                                       _vp]),
 }
 
 

@@ -1013,6 +1013,44 @@ int dc_spline_bwd_b(const int64_t *src, const int64_t *dst, const int32_t *ptr, 
 int dc_spline_bwd_a(const float *gb, const float *a, int64_t lda, const int64_t *ks, const int32_t *open,
                     int64_t degree, float *ga, int64_t ldga, int64_t E, int64_t D, dc_stream_t stream);
 
+/* ---- Point-set sampling and transfer (dc_pointops.hip; PyG fps, knn_interpolate) ----
+ * Distances as in the neighbour search: d2 = ((dx*dx + dy*dy) + dz*dz) in fp32, each operation rounded on its own.
+ * Fixed order, no float atomics, no host read: deterministic and capturable.  Inputs are taken to be finite.  Arguments
+ * are checked before any HIP call: sizes, leading dimensions, then null pointers, then aliasing.
+ *   dc_fps : farthest point sampling of B graphs, one workgroup per graph.  x fp32 [N, >= 3] (leading dimension ldx).
+ *            ptr int64 [B+1]: graph g owns the nodes [ptr[g], ptr[g+1]); optr int64 [B+1]: it writes the picks
+ *            out[optr[g] .. optr[g+1]) (int64 global node ids, pick order).  ptr = optr = NULL: one graph of N nodes and
+ *            M picks (B <= 1).  start int64 [B]: the first pick of every graph as a global node id (NULL, or a value
+ *            outside the graph: its first node).  Then, dist = +inf and c = the start: for every further pick
+ *            dist[j] = min(dist[j], d2(j, c)), c = the j with the largest dist[j], the lowest j among equals.  A graph
+ *            without nodes or without picks is skipped, as is one whose offsets do not fit N and M.  max_n: at least
+ *            the largest node count of a graph (a larger graph gets -1 picks).  max_n <= DC_FPS_RESIDENT_POINTS: points
+ *            and distances stay in registers, no workspace.  Larger: dc_fps_workspace_bytes(N, max_n) = 16 N bytes,
+ *            16-byte aligned, hold (x, y, z, dist) per node.  N == 0, B == 0, M == 0 or max_n == 0 returns DC_OK before
+ *            the null check.  One launch.
+ *   dc_knn_interpolate_fwd : x fp32 [Nx, F], pos_x [Nx, >= 3], pos_y [Ny, >= 3]; nbr int32 [Ny, k] and counts int32
+ *            [Ny] as dc_neighbors_fill wrote them (rank order, -1 padding); 1 <= k <= DC_NEIGHBORS_MAX_CAP.  Per query
+ *            i, over r < counts[i], j = nbr[i*k + r]: w = 1.0f / max(d2(pos_x[j], pos_y[i]), 1e-16f) (a true division);
+ *            num[c] = num[c] + w * x[j,c] and den = den + w from 0 in rank order (product and sum rounded separately);
+ *            y[i,c] = num[c] / den; a query without a neighbour gets a row of zeros.  w fp32 [Ny, k] (0 in the padding)
+ *            and den fp32 [Ny] are written too when given (both or neither).  Any F >= 1; 16-byte accesses when F % 4
+ *            == 0 and x, y and their row strides allow it.  Ny == 0 returns DC_OK before the null check.
+ *   dc_knn_interpolate_bwd : ptr int64 [Nx+1], slots int64: slots[ptr[j] .. ptr[j+1]) are the positions s = i*k + r with
+ *            nbr[s] == j, ascending.  gx[j,c] = the compensated sum, in that order, of w[s] * (gy[i,c] / den[i]); a
+ *            source without a slot gets a zero row; every row of gx is written exactly once.  Nx == 0 returns DC_OK
+ *            before the null check. */
+#define DC_FPS_RESIDENT_POINTS 8192
+int64_t dc_fps_resident_points(void);
+int64_t dc_fps_workspace_bytes(int64_t N, int64_t max_n);
+int dc_fps(const float *x, int64_t ldx, int64_t N, const int64_t *ptr, const int64_t *optr, int64_t B, int64_t max_n,
+           const int64_t *start, int64_t *out, int64_t M, void *workspace, int64_t workspace_bytes, dc_stream_t stream);
+int dc_knn_interpolate_fwd(const float *x, int64_t ldx, const float *pos_x, int64_t ldpx, const float *pos_y,
+                           int64_t ldpy, const int32_t *nbr, const int32_t *counts, int k, float *y, int64_t ldy,
+                           float *w, float *den, int64_t Nx, int64_t Ny, int64_t F, dc_stream_t stream);
+int dc_knn_interpolate_bwd(const int64_t *ptr, const int64_t *slots, const float *w, const float *den, const float *gy,
+                           int64_t ldgy, float *gx, int64_t ldgx, int k, int64_t Nx, int64_t Ny, int64_t F,
+                           dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

@@ -233,6 +233,15 @@ _SIGNATURES = {
                                        c_int64, c_int64, c_int64, _vp]),
     "dc_knn_interpolate_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int, c_int64, c_int64, c_int64,
                                        _vp]),
+    "dc_pointnet_pair_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64,
+                                     c_int64, c_int64, c_int, c_int, _vp]),
+    "dc_pointnet_pair_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp,
+                                     c_int64, c_int64, c_int64, c_int64, c_int64, c_int, _vp]),
+    "dc_pointnet_reduce_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp,
+                                       c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int, _vp]),
+    "dc_pool_fwd": (c_int, [_vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int, c_int64, c_int64, c_int64, _vp]),
+    "dc_pool_bwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int,
+                            c_int64, c_int64, c_int64, _vp]),
 }
 
 

@@ -1,5 +1,5 @@
 // dc_segment.h -- the device and host helpers the segment kernels share (dc_gat*.hip, dc_gatv2.hip, dc_transformer.hip,
-// dc_sage.hip, dc_gine.hip, dc_edge.hip, dc_gmm.hip, dc_gnn_epi.hip).  Internal; not for the dense / hop / attention translation units.
+// dc_sage.hip, dc_gine.hip, dc_edge.hip, dc_gmm.hip, dc_gnn_epi.hip, dc_pointnet.hip).  Internal; not for the dense / hop / attention translation units.
 //
 // These kernels promise: every sum in a fixed order, products and sums rounded separately, no float atomics - two runs
 // give the same bits.  The promise rests on the exact operation order of the helpers below, so each is defined ONCE,
@@ -74,6 +74,39 @@ template <int VEC>
 __device__ __forceinline__ void ints_store(int32_t *p, const int (&v)[VEC]) {
     if constexpr (VEC == 4) *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
     else *p = v[0];
+}
+
+// the per-column part of the backward of a sum / mean / max of rows gathered by an index (the pool and the PointNetConv
+// reduction, dc_pointnet.hip): one output row from the row g of the reduced side.  mode (wave-uniform): 0 a copy of
+// g_row; 1 that divided by deg; 2 the even split of the max - (v_row[c] == y_row[c]) ? g_row[c] / float(cnt_row[c]) : 0.
+// !ok: a zero row, and no pointer is dereferenced but out_row.  v_row, y_row, cnt_row are read for the max alone.
+template <int VEC>
+__device__ __forceinline__ void reduce_bwd_cols(int mode, bool ok, float deg, const float *__restrict__ v_row,
+                                                const float *__restrict__ y_row, const int32_t *__restrict__ cnt_row,
+                                                const float *__restrict__ g_row, float *__restrict__ out_row, int sub,
+                                                int L, int C) {
+    for (int c = sub * VEC; c < C; c += L * VEC) {
+        const Cols<VEC> gv = cols_load<VEC>(g_row + c, ok);
+        float out[VEC];
+        if (mode == 2) {
+            const Cols<VEC> mv = cols_load<VEC>(v_row + c, ok);
+            const Cols<VEC> yv = cols_load<VEC>(y_row + c, ok);
+            const Ints<VEC> cv = ints_load<VEC>(cnt_row + c, ok);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const bool hit = ok && mv.a[k] == yv.a[k] && cv.a[k] > 0;
+                const float share = gv.a[k] / (float)(hit ? cv.a[k] : 1);
+                out[k] = hit ? share : 0.f;
+            }
+        } else if (mode == 1) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) out[k] = ok ? gv.a[k] / deg : 0.f;
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) out[k] = gv.a[k];      // (!ok: loaded as zeros)
+        }
+        cols_store<VEC>(out_row + c, out);
+    }
 }
 
 // ---- cross-lane sums: fixed xor butterflies, widest step first; every lane of the group gets the result ---------------

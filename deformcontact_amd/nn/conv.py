@@ -1041,5 +1041,115 @@ class EdgeConv(_ConvBase):
         return f"{self.__class__.__name__}(nn={self.nn})"
 
 
+def _pointnet_pos(pos, what: str) -> Tensor:
+    """One position operand of ``PointNetConv``, checked in the order type, dtype, shape - before the device check of
+    ``neighbors._check_points``, which repeats them and adds the stride rule."""
+    if not isinstance(pos, Tensor):
+        raise TypeError(f"PointNetConv: {what} must be a tensor, got {type(pos).__name__}")
+    if pos.dtype != torch.float32:
+        raise ValueError(f"PointNetConv: {what} must be float32, got {pos.dtype}")
+    if pos.dim() != 2 or pos.size(1) != 3:
+        raise ValueError(f"PointNetConv: {what} must be [N, 3] positions (position widths other than 3 are not "
+                         f"supported), got {tuple(pos.shape)}")
+    return pos
+
+
+class PointNetConv(_ConvBase):
+    """PyG 2.5.2 ``PointNetConv`` (the set-abstraction layer of PointNet++): ``out_i = global_nn(aggr_j local_nn([x_j,
+    pos_j - pos_i]))`` over the incoming edges ``j -> i``.  Call ``conv(x, pos, edge_index)``.  ``x``: None (the message
+    is the 3 position columns alone), a float32 ``[Ns, F]`` tensor, or a pair ``(x_src, x_dst)`` of which only ``x_src``
+    is read, as in PyG (``x_dst`` may be None).  ``pos``: float32 ``[N, 3]`` or a pair ``(pos_src [Ns, 3], pos_dst
+    [Nd, 3])``, as ``neighbors`` takes positions (on the device, a row stride allowed).  The output has ``Nd`` rows.
+    ``local_nn`` and ``global_nn`` are any ``torch.nn.Module`` or None and are called as they are, once: ``local_nn`` on
+    the ``[E', F + 3]`` rows of all edges in the order of ``edge_index``; its result must be float32 ``[E', C]``.  Where
+    ``F % 4 == 0`` those rows come as a NON-CONTIGUOUS view (unit inner stride, row stride ``F + 4``, the padding column
+    zero) - ``Linear``, norms and activations take it as it is; a module that calls ``.view()`` on its input must call
+    ``.contiguous()`` first (``ops.POINTNET_PAD_Z = False`` gives contiguous rows everywhere).
+    ``aggr``: ``"max"`` (default), ``"mean"``, ``"sum"`` or its alias ``"add"``.
+
+    BIPARTITE input - a pair ``pos`` or ``x`` - needs ``add_self_loops=False`` (the form PointNet++ uses); with the
+    default ``True`` it is a ``ValueError``.  ``add_self_loops=True`` on one node set is PyG's remove-then-add without a
+    host read: ``E' = E + N``, the input edges in input order, then node ``i``'s loop at row ``E + i`` with the message
+    row ``[x_i, 0, 0, 0]``; an input edge with ``src == dst`` keeps its row - ``local_nn`` sees it - but its result takes
+    no part in the reduction and its gradient row is zero.
+
+    The pair rows and the reduction are one autograd node each on the kernels of dc_pointnet.hip and dc_edge.hip
+    (``ops.pointnet_pairs``, ``ops.pointnet_aggregate``): every sum in a fixed order, no float atomics, the gradient of
+    a maximum in equal shares to all edge rows that attain it, forward and backward
+    capturable.  The layer's result is ``global_nn``'s (or the reduction's), so there is no ``relu=`` / ``next_conv=`` and
+    no deferred result; a deferred ``x`` is resolved.  Not supported: position widths other than 3, aggregation lists or
+    modules, bf16-stored input, the deprecated ``PointConv`` name, ``SparseTensor`` adjacencies, ``PPFConv`` / ``XConv``."""
+
+    def __init__(self, local_nn: Optional[nn.Module] = None, global_nn: Optional[nn.Module] = None,
+                 add_self_loops: bool = True, aggr: str = "max"):
+        super().__init__()
+        if not isinstance(aggr, str) or aggr not in ("max", "mean", "sum", "add"):
+            raise ValueError(f"PointNetConv: aggr must be 'max', 'mean', 'sum' or 'add', got {aggr!r}")
+        self.local_nn = local_nn
+        self.global_nn = global_nn
+        self.add_self_loops = bool(add_self_loops)
+        self._self_loops = self.add_self_loops
+        self.aggr = "sum" if aggr == "add" else aggr
+
+    def reset_parameters(self):
+        for module in (self.local_nn, self.global_nn):
+            if module is not None:
+                _reset_module(module)
+
+    def _operands(self, x, pos):
+        """-> (x_src or None, pos_src, pos_dst), every host check that needs no device done"""
+        pair = isinstance(pos, (tuple, list)) or isinstance(x, (tuple, list))
+        if pair and self.add_self_loops:
+            raise ValueError("PointNetConv: bipartite input (a pair pos or x) needs add_self_loops=False; pass "
+                             "PointNetConv(..., add_self_loops=False)")
+        for name, v in (("pos", pos), ("x", x)):
+            if isinstance(v, (tuple, list)) and len(v) != 2:
+                raise ValueError(f"PointNetConv: a pair {name} must have 2 entries, got {len(v)}")
+        pos_src, pos_dst = pos if isinstance(pos, (tuple, list)) else (pos, pos)
+        pos_src, pos_dst = _pointnet_pos(pos_src, "pos_src"), _pointnet_pos(pos_dst, "pos_dst")
+        x_src, x_dst = x if isinstance(x, (tuple, list)) else (x, x)
+        for name, v, rows in (("x_src", x_src, pos_src.size(0)), ("x_dst", x_dst, pos_dst.size(0))):
+            if v is None:
+                continue
+            v = resolve(v)
+            if not isinstance(v, Tensor):
+                raise TypeError(f"PointNetConv: {name} must be a tensor or None, got {type(v).__name__}")
+            if name == "x_src":
+                x_src = v
+                if v.dtype != torch.float32:
+                    raise ValueError(f"PointNetConv: x must be float32, got {v.dtype}")
+                if v.dim() != 2 or v.size(1) == 0:
+                    raise ValueError(f"PointNetConv: x must be [Ns, F >= 1], got {tuple(v.shape)}")
+            if v.dim() >= 1 and v.size(0) != rows:
+                raise ValueError(f"PointNetConv: {name} has {v.size(0)} rows but its positions have {rows}")
+        return x_src, pos_src, pos_dst
+
+    def forward(self, x, pos, edge_index: Tensor) -> Tensor:
+        """``conv(x, pos, edge_index)`` as PyG; ``x`` and ``pos`` may be pairs (class docstring)."""
+        x_src, pos_src, pos_dst = self._operands(x, pos)
+        if not isinstance(edge_index, Tensor):
+            raise TypeError(f"PointNetConv: edge_index must be an int64 [2, E] tensor, got {type(edge_index).__name__} "
+                            "(SparseTensor adjacencies are not supported)")
+        for name, t in (("pos", pos_src), ("pos", pos_dst), ("x", x_src), ("edge_index", edge_index)):
+            if t is not None:
+                _require_cuda(t, name)
+                if t.device != pos_src.device:
+                    raise RuntimeError(f"pos is on {pos_src.device} but {name} is on {t.device}")
+        ns, nd, loops = pos_src.size(0), pos_dst.size(0), self.add_self_loops
+        g = ops.pointnet_graph(edge_index, ns, nd, loops) if max(ns, nd) else None
+        z = ops.pointnet_pairs(g, x_src, pos_src, pos_dst, loops)
+        m = resolve(self.local_nn(z)) if self.local_nn is not None else z
+        if not isinstance(m, Tensor) or m.dim() != 2 or m.dtype != torch.float32 or m.size(0) != z.size(0) \
+                or m.size(1) == 0:
+            got = f"{tuple(m.shape)} {m.dtype}" if isinstance(m, Tensor) else type(m).__name__
+            raise ValueError(f"PointNetConv: local_nn must return a float32 [E', C >= 1] tensor with E' = {z.size(0)} "
+                             f"rows, got {got}")
+        out = ops.pointnet_aggregate(g, m, self.aggr, nd, loops)
+        return self.global_nn(out) if self.global_nn is not None else out
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}(local_nn={self.local_nn}, global_nn={self.global_nn})"
+
+
 # ``models/model.py:2`` imports ``knn`` from here (it never calls it): the device search of ``neighbors``
 from ..neighbors import knn  # noqa: E402,F401

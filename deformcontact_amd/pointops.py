@@ -1,5 +1,6 @@
-"""Point-set sampling and transfer on the device: PyG 2.5's ``fps`` and ``knn_interpolate`` on the HIP kernels of
-``csrc/dc_pointops.hip`` (``dc_fps`` / ``dc_knn_interpolate_fwd`` / ``dc_knn_interpolate_bwd``).
+"""Point-set sampling, transfer and pooling on the device: PyG 2.5's ``fps`` and ``knn_interpolate`` on the HIP kernels
+of ``csrc/dc_pointops.hip`` (``dc_fps`` / ``dc_knn_interpolate_fwd`` / ``dc_knn_interpolate_bwd``), and ``global_add_pool``
+/ ``global_mean_pool`` / ``global_max_pool`` on those of ``csrc/dc_pointnet.hip`` (``dc_pool_fwd`` / ``dc_pool_bwd``).
 
 ``fps`` is the sampling step of PointNet++ set abstraction (the grouping step is ``neighbors.radius``);
 ``knn_interpolate`` is its feature propagation: node rows of one point set carried onto another by
@@ -44,6 +45,22 @@ Where PyG's own rule is unspecified - which of several equally far points is tak
    on the device (a stable sort of the flattened neighbour array), in the backward only.
 5. No host read anywhere: forward and backward may be recorded in ``torch.cuda.graph``.  No float atomics: two runs
    give the same bits.
+
+``global_add_pool(x, batch, size=None)``, ``global_mean_pool``, ``global_max_pool`` ``-> float32 [B, C]``
+
+1. ``x`` is float32 ``[N, C >= 1]`` with unit inner stride (a column slice passes as it is; a deferred result is
+   resolved).  ``batch`` is a sorted int64 ``[N]`` vector of graph ids; ``batch=None`` is one graph and gives ``[1, C]``
+   (``size`` is then ignored, as in PyG).
+2. ``size=None`` reads the graph count ``batch[-1] + 1`` once on the host, as ``fps`` does.  With ``size`` the call
+   reads nothing on the host and may be recorded in ``torch.cuda.graph``; rows whose id is not below ``size`` take no
+   part and get a zero gradient.  The row offsets of the graphs are made on the device (``torch.searchsorted``).
+3. A graph id without rows gets 0.  The mean divides the sum by ``float(rows)`` (a true division).  The max sends its
+   gradient in equal shares to ALL rows that attain it; an int32 count per output is saved.
+4. Order of the sums: one workgroup per (graph, column block) of 16 slots; slot ``s`` adds the
+   rows ``a + s, a + s + 16, ...`` in ascending order from 0, and the 16 partial sums are added in slot order, all plain
+   fp32 - a numpy loop reproduces every bit.  Per graph it stays one workgroup per column block: a cooperative form
+   that spreads ONE huge cloud over the device is not built (as for ``fps``).
+5. Each function is one autograd node with one launch forward and one backward; no float atomics.
 """
 from __future__ import annotations
 
@@ -237,3 +254,83 @@ def knn_interpolate(x: Tensor, pos_x: Tensor, pos_y: Tensor, batch_x: Optional[T
     with torch.no_grad():
         nbr, counts = neighbors.knn_padded(pos_x, pos_y, k, batch_x, batch_y)
     return _KnnInterpolateFn.apply(_feature_rows(x), pos_x, pos_y, nbr, counts)
+
+
+#: the rows of one graph are dealt to this many slots of a workgroup (dc_pointnet.hip kPoolSlots): the order of the sums
+POOL_SLOTS = 16
+_POOL_MODES = {"add": 0, "mean": 1, "max": 2}
+
+
+class _GlobalPoolFn(torch.autograd.Function):
+    """One launch forward, one backward.  ``batch`` and the graph offsets are saved for the backward (autograd's version
+    check covers them); the max also saves ``x``, ``y`` and the tie counts."""
+
+    @staticmethod
+    def forward(ctx, x, batch, ptr, nb: int, mode: int):
+        n, c = x.shape
+        ctx.mode, ctx.nb, ctx.shape = mode, nb, (n, c)
+        y = torch.empty(nb, c, dtype=torch.float32, device=x.device)
+        if nb == 0:
+            return y
+        cnt = torch.empty(nb, c, dtype=torch.int32, device=x.device) if mode == 2 else None
+        _lib.check(_lib.lib().dc_pool_fwd(None if ptr is None else ptr.data_ptr(), x.data_ptr() if n else None, _ldf(x),
+                                          y.data_ptr(), c, None if cnt is None else cnt.data_ptr(), c, mode, n, nb, c,
+                                          current_stream_ptr(x.device)), "dc_pool_fwd")
+        ctx.save_for_backward(batch, ptr, *((x, y, cnt) if mode == 2 else (None, None, None)))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        n, c = ctx.shape
+        if n == 0 or ctx.nb == 0:
+            return gy.new_zeros(n, c), None, None, None, None
+        batch, ptr, x, y, cnt = ctx.saved_tensors
+        gy = _grad_rows(gy)
+        gx = torch.empty(n, c, dtype=torch.float32, device=gy.device)
+        p = lambda t: None if t is None else t.data_ptr()
+        _lib.check(_lib.lib().dc_pool_bwd(p(batch), p(ptr), p(x), _ldf(x) if x is not None else c, p(y), c, p(cnt),
+                                          c, gy.data_ptr(), _ldf(gy), gx.data_ptr(), c, ctx.mode, n, ctx.nb, c,
+                                          current_stream_ptr(gy.device)), "dc_pool_bwd")
+        return gx, None, None, None, None
+
+
+def _global_pool(who: str, x: Tensor, batch: Optional[Tensor], size, mode: str) -> Tensor:
+    x = resolve(x)
+    if not isinstance(x, Tensor):
+        raise TypeError(f"{who}: x must be a tensor (got {type(x).__name__})")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.size(1) == 0:
+        raise ValueError(f"{who}: x must be a float32 [N, C >= 1] tensor, got {tuple(x.shape)} {x.dtype}")
+    if batch is not None and isinstance(batch, Tensor) and (batch.dtype != torch.int64 or batch.dim() != 1
+                                                              or batch.numel() != x.size(0)):
+        raise ValueError(f"{who}: batch must be a sorted int64 vector of {x.size(0)} graph ids (got {batch.dtype} "
+                         f"{tuple(batch.shape)})")
+    if size is not None:
+        size = operator.index(size)
+        if size < 0:
+            raise ValueError(f"{who}: size must be >= 0 (got {size})")
+    _require_cuda(x, "x")
+    batch = neighbors._check_batch(batch, x.size(0), x.device, "batch")
+    x = _feature_rows(x)
+    if batch is None:
+        return _GlobalPoolFn.apply(x, None, None, 1, _POOL_MODES[mode])
+    if size is None:
+        size = int(batch[-1]) + 1 if batch.numel() else 0        # the one host read
+    ptr = torch.searchsorted(batch, torch.arange(size + 1, dtype=torch.int64, device=x.device))
+    return _GlobalPoolFn.apply(x, batch, ptr, size, _POOL_MODES[mode])
+
+
+def global_add_pool(x: Tensor, batch: Optional[Tensor], size: Optional[int] = None) -> Tensor:
+    """PyG ``global_add_pool``: the sum of the rows of every graph, float32 ``[B, C]``.  Rules: module docstring."""
+    return _global_pool("global_add_pool", x, batch, size, "add")
+
+
+def global_mean_pool(x: Tensor, batch: Optional[Tensor], size: Optional[int] = None) -> Tensor:
+    """PyG ``global_mean_pool``: the mean of the rows of every graph, float32 ``[B, C]``; a graph without rows gets 0.
+    Rules: module docstring."""
+    return _global_pool("global_mean_pool", x, batch, size, "mean")
+
+
+def global_max_pool(x: Tensor, batch: Optional[Tensor], size: Optional[int] = None) -> Tensor:
+    """PyG ``global_max_pool``: the maximum per column of the rows of every graph, float32 ``[B, C]``; a graph without
+    rows gets 0; the gradient goes in equal shares to all rows that attain the maximum.  Rules: module docstring."""
+    return _global_pool("global_max_pool", x, batch, size, "max")

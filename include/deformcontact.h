@@ -1051,6 +1051,51 @@ int dc_knn_interpolate_bwd(const int64_t *ptr, const int64_t *slots, const float
                            int64_t ldgy, float *gx, int64_t ldgx, int k, int64_t Nx, int64_t Ny, int64_t F,
                            dc_stream_t stream);
 
+/* ---- PointNetConv and global pooling (dc_pointnet.hip; PyG point_conv.py, global_*_pool) ----
+ * The per-edge primitives of PointNet++ set abstraction on a BIPARTITE edge set - sources x_src [n_src, F] / pos_src
+ * [n_src, >= 3], destinations pos_dst [n_dst, >= 3], src / dst the int64 rows of the edge list - and the per-graph
+ * pooling.  The sorted sets are those of ONE adjacency over max(n_src, n_dst) rows (dc_graph_build): ptr / other / perm
+ * by destination, ptr_t / other_t / perm_t by source.  loops != 0 (n_src == n_dst == N, the adjacency built with
+ * self_loops): E + N edge rows, node i's loop at row E + i and LAST in its groups; an input edge with src == dst takes
+ * no part.  Rules of dc_edge_*: fixed order, no float atomics, no host read, any width, 16-byte accesses where widths,
+ * strides and pointers allow it.  Arguments are checked before any HIP call: sizes, leading dimensions, nulls, aliasing.
+ *   dc_pointnet_pair_fwd   : z [E', F + 3]: z[q,:F] = x_src[src[q]] (a copy), z[q,F+d] = pos_src[src[q],d] -
+ *            pos_dst[dst[q],d] (one fp32 subtraction); a loop row [x_src[i], +0, +0, +0].  src[q] outside [0, n_src) or
+ *            dst[q] outside [0, n_dst): a zero row.  F == 0 is legal (x may be NULL).  zpad (0..3): that many further
+ *            columns behind F + 3 are written as zeros (ldz >= F + 3 + zpad; the padding of a row stride rounded up to
+ *            4 floats).  No row returns DC_OK.
+ *   dc_pointnet_pair_bwd   : one lane group per node r < max(n_src, n_dst), compensated sums in the order of the sorted
+ *            sets: gx[r,c] over gz[perm_t[t],c] (the loop row included), gpos_src[r,d] over gz[perm_t[t],F+d] and
+ *            gpos_dst[r,d] = -(the sum over gz[perm[p],F+d]), both over input edges (id < E) alone; an edge whose other
+ *            endpoint is outside its node set is left out.  Each of gx, gpos_src, gpos_dst may be NULL (skipped).
+ *   dc_pointnet_reduce_bwd : the per-row gradient gm [E', C] of dc_edge_reduce_fwd over such a set (mode 0 sum, 1 mean,
+ *            2 max with the even split among all rows that attain the maximum): i = dst[q], or q - E for a loop row;
+ *            the mean divides by ptr[i+1] - ptr[i] (the loop counts).  A zero row for dst[q] outside [0, n_dst), src[q]
+ *            outside [0, n_all) (n_all >= n_dst: the rows of the adjacency) and, with loops, src[q] == dst[q].
+ *   dc_pool_fwd : y [B, C] = sum (mode 0) / mean (1) / max (2, cnt int32 [B, C] = the rows that attain it) of the rows
+ *            [ptr[g], ptr[g+1]) of x [N, C] (ptr int64 [B+1]; NULL: one graph [0, N), B == 1).  One workgroup per
+ *            (graph, block of 16 (64 with 16-byte access) columns): 16 slots of 16 lanes, slot s takes the rows a + s,
+ *            a + s + 16, ... in ascending order from 0 (-inf), the 16 partial results are merged in slot order.  A graph
+ *            without rows gets 0 (cnt 0).  B == 0 returns DC_OK.
+ *   dc_pool_bwd : gx [N, C]: g = batch[r] (NULL with ptr NULL: one graph): gy[g] (sum), gy[g] / float(rows of g) (mean),
+ *            (x[r,c] == y[g,c]) ? gy[g,c] / float(cnt[g,c]) : 0 (max); g outside [0, B): a zero row.  N == 0: DC_OK. */
+int dc_pointnet_pair_fwd(const int64_t *src, const int64_t *dst, const float *x, int64_t ldx, const float *pos_src,
+                         int64_t ldps, const float *pos_dst, int64_t ldpd, float *z, int64_t ldz, int64_t n_src,
+                         int64_t n_dst, int64_t E, int64_t F, int loops, int zpad, dc_stream_t stream);
+int dc_pointnet_pair_bwd(const int32_t *ptr, const int32_t *other, const int32_t *perm, const int32_t *ptr_t,
+                         const int32_t *other_t, const int32_t *perm_t, const float *gz, int64_t ldgz, float *gx,
+                         int64_t ldgx, float *gpos_src, int64_t ldgps, float *gpos_dst, int64_t ldgpd, int64_t n_src,
+                         int64_t n_dst, int64_t E, int64_t F, int loops, dc_stream_t stream);
+int dc_pointnet_reduce_bwd(const int64_t *src, const int64_t *dst, const int32_t *ptr, const float *m, int64_t ldm,
+                           const float *y, int64_t ldy, const int32_t *cnt, int64_t ldc, const float *gy, int64_t ldgy,
+                           float *gm, int64_t ldgm, int mode, int64_t n_all, int64_t n_dst, int64_t E, int64_t C,
+                           int loops, dc_stream_t stream);
+int dc_pool_fwd(const int64_t *ptr, const float *x, int64_t ldx, float *y, int64_t ldy, int32_t *cnt, int64_t ldc,
+                int mode, int64_t N, int64_t B, int64_t C, dc_stream_t stream);
+int dc_pool_bwd(const int64_t *batch, const int64_t *ptr, const float *x, int64_t ldx, const float *y, int64_t ldy,
+                const int32_t *cnt, int64_t ldc, const float *gy, int64_t ldgy, float *gx, int64_t ldgx, int mode,
+                int64_t N, int64_t B, int64_t C, dc_stream_t stream);
+
 /* ---- packing helpers of the narrow-layer path (F_in = 21 / 25) ----------------
  * A TAGConv layer whose K+1 column blocks are narrow runs its dense block over ONE K segment:
  * the hop slab [N, wpad] (wpad = (K+1)*F rounded up to 16).  pack_input: slab[:, 0:F] = x and

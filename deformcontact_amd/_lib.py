@@ -87,6 +87,8 @@ _SIGNATURES = {
                                   _vp, _vp, _vp, c_int64, _vp]),
     "dc_neighbors_compact_workspace_bytes": (c_int64, [c_int64]),
     "dc_neighbors_compact": (c_int, [_vp, c_int, _vp, c_int64, c_int, _vp, c_int64, _vp, c_int64, _vp]),
+    "dc_neighbors_nd_fill": (c_int, [_vp, c_int64, c_int64, _vp, _vp, c_int64, c_int64, _vp, c_int64, c_int, c_int,
+                                     _vp, _vp, _vp]),
     "dc_spmm_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
                             c_int64, _vp]),
     "dc_spmm_bf16": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,

@@ -25,6 +25,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "dc_common.h"
+#include "dc_topk.h"
 
 namespace dc {
 namespace {
@@ -33,7 +34,7 @@ constexpr int kMaxCap = DC_NEIGHBORS_MAX_CAP;   // one kept neighbour per lane o
 constexpr int kMaxDim = 1024;                   // cells per axis of a graph's grid: a cell id fits 30 bits
 constexpr int kBboxChunk = 1024;                // points per wave in k_seg_bbox
 constexpr int kMaxSteps = 4096;                 // box growth steps (a finite query needs at most ~kMaxDim + 2)
-constexpr unsigned long long kNone = ~0ull;     // an empty top-k slot; every real key is smaller
+constexpr unsigned long long kNone = kTopkNone;  // an empty top-k slot (dc_topk.h); every real key is smaller
 
 // a graph's grid, stored at the index of the graph's first point (its segment start)
 struct GridParams {
@@ -42,38 +43,10 @@ struct GridParams {
     int dims[3], pad;
 };
 
-__device__ __forceinline__ unsigned ord_key(float f) {          // order-preserving map float -> unsigned
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord_val(unsigned u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
 // the ONE cell map of points and of box bounds: monotone in v for any positive inv (NaN and +-inf clamp to the grid)
 __device__ __forceinline__ int cell_of(float v, const GridParams &P, int a) {
     const float t = floorf(__fmul_rn(__fsub_rn(v, P.lo[a]), P.inv));
     return (int)fminf(fmaxf(t, 0.0f), (float)(P.dims[a] - 1));
-}
-
-// first index in [lo, hi) whose value is >= v (hi if none)
-template <typename T>
-__device__ __forceinline__ int64_t lower_bound(const T *a, int64_t lo, int64_t hi, T v) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-template <typename T>
-__device__ __forceinline__ int64_t upper_bound(const T *a, int64_t lo, int64_t hi, T v) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 __global__ void __launch_bounds__(256)
@@ -321,19 +294,7 @@ k_query(const float *__restrict__ y, int64_t ldy, int64_t ny, const int64_t *__r
                                 key = ((unsigned long long)ord_key(d2) << 32) | (unsigned)j;
                         }
                         // insert the candidates below the current cap-th key, one at a time, keeping lanes sorted
-                        unsigned long long m = __ballot(key < kth);
-                        while (m) {
-                            const int src = __ffsll((unsigned long long)m) - 1;
-                            m &= m - 1;
-                            const unsigned long long c = __shfl(key, src);
-                            if (c < kth) {
-                                const int pos = __popcll(__ballot(entry < c));
-                                const unsigned long long up = __shfl_up(entry, 1);
-                                if (lane == pos) entry = c;
-                                else if (lane > pos && lane < cap) entry = up;
-                                kth = __shfl(entry, cap - 1);
-                            }
-                        }
+                        topk_insert(key, lane, cap, entry, kth);
                     }
                 }
 #pragma unroll
@@ -350,9 +311,7 @@ k_query(const float *__restrict__ y, int64_t ldy, int64_t ny, const int64_t *__r
             rho = radius_mode ? fminf(next, rho_max) : next;
         }
     }
-    const int count = __popcll(__ballot(entry != kNone));
-    if (lane < cap) nbr[q * cap + lane] = lane < count ? (int32_t)(unsigned)entry : -1;
-    if (lane == 0) counts[q] = count;
+    topk_store(entry, lane, cap, nbr + q * cap, counts + q);
 }
 
 __global__ void __launch_bounds__(256)

@@ -1,5 +1,6 @@
 """kNN and radius graphs on the device: PyG 2.5's ``knn``, ``knn_graph``, ``radius`` and ``radius_graph`` on the HIP
-kernels of ``csrc/dc_neighbors.hip`` (``dc_neighbors_fill`` / ``dc_neighbors_compact``).
+kernels of ``csrc/dc_neighbors.hip`` (``dc_neighbors_fill`` / ``dc_neighbors_compact``) and, for rows of any other
+width - the feature-space search of DGCNN - ``csrc/dc_neighbors_nd.hip`` (``dc_neighbors_nd_fill``).
 
 The reference builds point-cloud graphs with ``radius_graph(pc, r, loop=False)`` / ``knn_graph(pc, k, loop=False)``
 (``/root/reference/utils/pointcloud_utils.py:7-13``).  Two layers:
@@ -14,9 +15,14 @@ The reference builds point-cloud graphs with ``radius_graph(pc, r, loop=False)``
 Rules (the contract):
 
 1. Positions are float32 HIP tensors ``[N, 3]`` (a row stride is allowed, the inner stride must be 1); a CPU tensor,
-   another width, float64 and ``cosine=True`` raise.  ``batch*`` are sorted int64 graph ids; a query's candidates
-   are the points of its own graph.  ``num_workers`` / ``batch_size`` are accepted and ignored.
-2. ``d2 = ((dx*dx + dy*dy) + dz*dz)`` in fp32, ``dx = x_j - y_i``, each product and sum rounded on its own.
+   float64 and ``cosine=True`` raise.  ``batch*`` are sorted int64 graph ids; a query's candidates are the points
+   of its own graph.  ``num_workers`` / ``batch_size`` are accepted and ignored.  The kNN functions also take rows
+   ``[N, F]`` of any other width ``F >= 1`` (features): an ``[N, 3]`` operand takes the grid search, any other width
+   the exact tiled brute force of ``knn_padded_nd`` (which takes ``F = 3`` too, with the same bits).  ``radius*``
+   stay three-dimensional.
+2. ``d2 = ((dx*dx + dy*dy) + dz*dz)`` in fp32, ``dx = x_j - y_i``, each product and sum rounded on its own.  At
+   width ``F``: ``d2 = d_0*d_0``, then ``d2 = d2 + d_c*d_c`` for ``c = 1 .. F-1`` in column order, ``d_c = x[j,c] -
+   y[i,c]``, every difference, product and sum rounded on its own - for ``F = 3`` the same formula.
 3. Candidates are ranked by ``(d2, j)`` ascending.  ``knn`` keeps the first ``k``.  ``radius`` keeps those with
    ``d2 < r2``, ``r2 = float32(r) * float32(r)`` rounded once, then the first ``max_num_neighbors`` by rank: under the
    cap, the nearest (PyG leaves that choice open; ``synth.radius_graph_points`` makes the same one).
@@ -41,6 +47,9 @@ from .graph import _require_cuda, current_stream_ptr
 
 #: the most neighbours one query keeps on this path (include/deformcontact.h DC_NEIGHBORS_MAX_CAP: a lane per rank)
 MAX_CAP = 64
+#: columns the width-F kernel stages per pass (include/deformcontact.h DC_NEIGHBORS_ND_CHUNK): widths below, at and
+#: above it and its multiples take different code paths, which is what the tests pick their widths by
+ND_CHUNK = 32
 _KNN, _RADIUS = 0, 1          # DC_NEIGHBORS_KNN / DC_NEIGHBORS_RADIUS
 _FLOWS = ("source_to_target", "target_to_source")
 
@@ -64,6 +73,30 @@ def _check_points(t: Tensor, what: str) -> None:
 
 def _ld(t: Tensor) -> int:
     return t.stride(0) if t.size(0) > 1 else 3
+
+
+def _check_rows(t: Tensor, what: str) -> None:
+    """``_check_points`` for the width-F search: any width ``>= 1``."""
+    if not isinstance(t, Tensor):
+        raise TypeError(f"{what} must be a tensor (got {type(t).__name__})")
+    _require_cuda(t, what)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32 (got {t.dtype}): distances are defined in fp32, rounded per "
+                        "operation, and a float64 search would rank near-ties differently")
+    if t.dim() != 2 or t.size(1) < 1:
+        raise ValueError(f"{what} must be [N, F] rows of width F >= 1 (got shape {tuple(t.shape)})")
+    if t.size(0) >= 2 ** 31 - 65:
+        raise ValueError(f"{what}: {t.size(0)} rows exceed int32 indexing")
+    if t.size(0) > 1 and (t.stride(1) != 1 or t.stride(0) < t.size(1)):
+        raise ValueError(f"{what} must have an inner stride of 1 and non-overlapping rows (got strides "
+                         f"{tuple(t.stride())} at width {t.size(1)})")
+
+
+def _is_nd(t) -> bool:
+    """Does this first operand of a kNN call take the width-F search?  A float32 device matrix of a width other than 3;
+    everything else goes to the grid path, which takes ``[N, 3]`` and refuses the rest as it always has."""
+    return isinstance(t, Tensor) and t.dim() == 2 and t.size(1) >= 1 and t.size(1) != 3 and t.is_cuda \
+        and t.dtype == torch.float32
 
 
 def _check_batch(b: Optional[Tensor], n: int, device, what: str) -> Optional[Tensor]:
@@ -124,7 +157,36 @@ def knn_padded(x: Tensor, y: Tensor, k: int, batch_x: Optional[Tensor] = None, b
     """The ``k`` nearest points of ``x`` to every point of ``y`` (rules 1-6 of the module docstring), without a host
     read: ``(nbr [Ny, k] int32, counts [Ny] int32)``; row ``i`` of ``nbr`` holds ``counts[i]`` indices into ``x`` in
     rank order, then ``-1``.  ``exclude_self`` drops ``j == i`` (``knn_graph(loop=False)``)."""
+    if _is_nd(x):
+        return knn_padded_nd(x, y, k, batch_x, batch_y, exclude_self)
     return _fill(x, y, _check_cap(k, "k"), None, batch_x, batch_y, exclude_self)
+
+
+def knn_padded_nd(x: Tensor, y: Tensor, k: int, batch_x: Optional[Tensor] = None, batch_y: Optional[Tensor] = None,
+                  exclude_self: bool = False) -> Tuple[Tensor, Tensor]:
+    """``knn_padded`` for rows of any width ``F >= 1`` (3 included: the grid path's bits): ``x [Nx, F]``, ``y [Ny,
+    F]`` float32 on one HIP device, unit inner stride, non-overlapping rows.  An exact brute force per graph on the
+    kernel of ``csrc/dc_neighbors_nd.hip`` - ``Ny x n_graph x F`` subtract / multiply / add triples, so it is the grid
+    path that wins on large three-dimensional clouds.  Same result layout, no host read, no workspace: capturable."""
+    cap = _check_cap(k, "k")
+    _check_rows(x, "x")
+    _check_rows(y, "y")
+    if x.device != y.device:
+        raise ValueError(f"x is on {x.device}, y on {y.device}")
+    if x.size(1) != y.size(1):
+        raise ValueError(f"x and y must have the same width (got {x.size(1)} and {y.size(1)} columns)")
+    dev, f = x.device, x.size(1)
+    nx, ny = x.size(0), y.size(0)
+    batch_x = _check_batch(batch_x, nx, dev, "batch_x")
+    batch_y = _check_batch(batch_y, ny, dev, "batch_y")
+    nbr = torch.empty(ny, cap, dtype=torch.int32, device=dev)
+    counts = torch.empty(ny, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().dc_neighbors_nd_fill(
+        x.data_ptr(), x.stride(0) if nx > 1 else f, nx, None if batch_x is None else batch_x.data_ptr(),
+        y.data_ptr(), y.stride(0) if ny > 1 else f, ny, None if batch_y is None else batch_y.data_ptr(),
+        f, cap, int(bool(exclude_self)), nbr.data_ptr(), counts.data_ptr(), current_stream_ptr(dev)),
+        "dc_neighbors_nd_fill")
+    return nbr, counts
 
 
 def radius_padded(x: Tensor, y: Tensor, r: float, batch_x: Optional[Tensor] = None,
@@ -185,7 +247,8 @@ def _no_cosine(cosine: bool) -> None:
 def knn(x: Tensor, y: Tensor, k: int, batch_x: Optional[Tensor] = None, batch_y: Optional[Tensor] = None,
         cosine: bool = False, num_workers: int = 1, batch_size: Optional[int] = None) -> Tensor:
     """PyG ``knn``: for every point of ``y`` its ``k`` nearest points of ``x`` in the same graph.  Returns
-    ``[2, M]`` int64: row 0 indexes ``y`` (the query), row 1 indexes ``x``.  Rules: module docstring."""
+    ``[2, M]`` int64: row 0 indexes ``y`` (the query), row 1 indexes ``x``.  ``[N, 3]`` positions or ``[N, F]``
+    feature rows.  Rules: module docstring."""
     _no_cosine(cosine)
     nbr, counts = knn_padded(x, y, k, batch_x, batch_y)
     return _edges(nbr, counts, 0)
@@ -196,7 +259,8 @@ def knn_graph(x: Tensor, k: int, batch: Optional[Tensor] = None, loop: bool = Fa
               batch_size: Optional[int] = None) -> Tensor:
     """PyG ``knn_graph``: every point's ``k`` nearest points of its graph.  ``flow="source_to_target"``:
     ``edge_index[0]`` is the neighbour, ``edge_index[1]`` the centre; ``"target_to_source"`` swaps the rows.
-    ``loop=False`` drops ``j == i``.  Rules: module docstring."""
+    ``loop=False`` drops ``j == i``.  ``[N, 3]`` positions or ``[N, F]`` feature rows (the graph DGCNN rebuilds in
+    every layer).  Rules: module docstring."""
     _no_cosine(cosine)
     query_row = _check_flow(flow)
     nbr, counts = knn_padded(x, x, k, batch, batch, exclude_self=not loop)

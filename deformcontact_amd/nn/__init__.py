@@ -10,9 +10,9 @@ graph construction (``knn``, ``knn_graph``, ``radius``, ``radius_graph``,
 """
 from ..neighbors import knn_graph, radius, radius_graph  # noqa: F401
 from ..pointops import fps, global_add_pool, global_max_pool, global_mean_pool, knn_interpolate  # noqa: F401
-from .conv import (ChebConv, EdgeConv, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, GMMConv, PointNetConv,  # noqa: F401
-                   SAGEConv, SplineConv, TAGConv, TransformerConv, knn)
+from .conv import (ChebConv, DynamicEdgeConv, EdgeConv, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv,  # noqa: F401
+                   GMMConv, PointNetConv, SAGEConv, SplineConv, TAGConv, TransformerConv, knn)
 
 __all__ = ["TAGConv", "GCNConv", "GATConv", "GATv2Conv", "TransformerConv", "knn", "knn_graph", "radius", "radius_graph",
-           "SAGEConv", "PointNetConv", "global_add_pool", "global_mean_pool", "global_max_pool", "GINConv", "GINEConv",
-           "EdgeConv", "fps", "knn_interpolate", "SplineConv", "GMMConv", "ChebConv"]
+           "DynamicEdgeConv", "SAGEConv", "PointNetConv", "global_add_pool", "global_mean_pool", "global_max_pool", "GINConv",
+           "GINEConv", "EdgeConv", "fps", "knn_interpolate", "SplineConv", "GMMConv", "ChebConv"]

@@ -45,6 +45,7 @@ from torch import Tensor
 from .. import ops
 from ..graph import GraphIndex, _require_cuda, graph_index
 from ..deferred import deferred, resolve
+from ..neighbors import MAX_CAP, knn_graph
 
 #: a plain ``conv(x, edge_index)`` call returns a ``deferred.DeferredActivation``: the ``F.relu`` the reference applies
 #: right behind it (``models/model.py:71,77``) then runs fused in the layer's epilogue, and the output lands in the hop
@@ -1039,6 +1040,46 @@ class EdgeConv(_ConvBase):
 
     def __repr__(self) -> str:
         return f"{self.__class__.__name__}(nn={self.nn})"
+
+
+class DynamicEdgeConv(EdgeConv):
+    """PyG 2.5.2 ``DynamicEdgeConv`` (DGCNN): ``EdgeConv`` on the kNN graph of its own input, rebuilt in feature space
+    at every call - ``conv(x, batch=None)`` is ``EdgeConv(nn, aggr)(x, knn_graph(x, k, batch, loop=True))``, i.e. PyG's
+    ``knn(x, x, k, batch, batch).flip([0])``: every point is among its own ``k`` neighbours, a graph with fewer than
+    ``k`` points gives all of them.  ``x``: float32 ``[N, F]`` of any width ``F >= 1`` on the device; ``batch``: sorted
+    int64 graph ids or None.  The search runs on the device (``neighbors.knn_graph``: three columns take the grid
+    search, any other width the exact brute force of dc_neighbors_nd.hip; rules 2-5 of ``neighbors``, so the edge set is
+    bit-for-bit reproducible) on ``x.detach()`` - no gradient goes through the choice of neighbours, as in PyG; the
+    gradient is ``EdgeConv``'s.  With ``batch`` the edge list carries the batch layout and the layer takes the one-launch
+    segmented adjacency build.  ``1 <= k <= 64`` (``neighbors.MAX_CAP``); ``num_workers`` is accepted and ignored.  The
+    layer reads the edge total on the host, as ``knn_graph`` does, so it is not capturable (a form on the padded
+    neighbour array is a later change).  Not supported: bipartite ``(x_src, x_dst)`` / ``(batch_src, batch_dst)`` input
+    (a ``TypeError``), ``cosine`` search, and what ``EdgeConv`` does not support."""
+
+    def __init__(self, nn: nn.Module, k: int, aggr: str = "max", num_workers: int = 1):
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_CAP:
+            raise ValueError(f"DynamicEdgeConv: k must be an integer in [1, {MAX_CAP}], got {k!r}")
+        if not isinstance(aggr, str) or aggr not in ("max", "mean", "sum", "add"):
+            raise ValueError(f"DynamicEdgeConv: aggr must be 'max', 'mean', 'sum' or 'add', got {aggr!r}")
+        super().__init__(nn, aggr)
+        self.k = k
+        self.num_workers = num_workers
+
+    def forward(self, x: Tensor, batch: Optional[Tensor] = None) -> Tensor:
+        """``conv(x, batch)`` as PyG; a deferred ``x`` is resolved."""
+        if isinstance(x, (tuple, list)) or isinstance(batch, (tuple, list)):
+            raise TypeError("DynamicEdgeConv: bipartite (x_src, x_dst) / (batch_src, batch_dst) input is not "
+                            "supported; pass one [N, F] tensor and one batch vector")
+        x = resolve(x)
+        if not isinstance(x, Tensor):
+            raise TypeError(f"DynamicEdgeConv: x must be a tensor, got {type(x).__name__}")
+        if x.dim() != 2:
+            raise ValueError("Static graphs not supported in DynamicEdgeConv")
+        edge_index = knn_graph(x.detach(), self.k, batch, loop=True, flow="source_to_target")
+        return super().forward(x, edge_index)
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}(nn={self.nn}, k={self.k})"
 
 
 def _pointnet_pos(pos, what: str) -> Tensor:

@@ -211,6 +211,29 @@ int dc_neighbors_compact(const int32_t *nbr, int cap, const int32_t *counts, int
                          int64_t *edge_index, int64_t num_edges, void *workspace, int64_t workspace_bytes,
                          dc_stream_t stream);
 
+/* ---- kNN over rows of any width (dc_neighbors_nd.hip; PyG knn / knn_graph in feature space, DynamicEdgeConv) ----
+ * dc_neighbors_nd_fill: dc_neighbors_fill's kNN mode for x fp32 [nx, f] and y fp32 [ny, f], f >= 1 (unit inner
+ *   stride, leading dimensions ldx, ldy >= f): an exact tiled brute force per graph, no grid and no workspace.
+ *     batch_x [nx], batch_y [ny]: sorted int64 graph ids, or NULL for "all in graph 0"; a query's candidates are
+ *       the rows of x with its own graph id, found on the device;
+ *     with d_c = x[j,c] - y[i,c]: d2 = d_0*d_0, then d2 = d2 + d_c*d_c for c = 1 .. f-1 IN COLUMN ORDER, every
+ *       difference, product and sum rounded on its own in fp32 (f = 3: the rule of dc_neighbors_fill, bit for bit);
+ *       never the |x|^2 + |y|^2 - 2 x.y form, never MFMA;
+ *     the candidates are ranked by (d2, j) ascending and the first `cap` kept; exclude_self != 0 drops j == i by
+ *       index (a duplicate row j != i stays, at distance 0).
+ *   Writes counts [ny] and nbr [ny, cap] in exactly dc_neighbors_fill's layout (rank order, then -1), so
+ *   dc_neighbors_compact and every other consumer take them unchanged.  0 <= cap <= DC_NEIGHBORS_MAX_CAP.  No atomics:
+ *   two calls are bit-identical.  Non-finite features: the ranking is unspecified; the kernel terminates and stays in
+ *   bounds.  Errors (DC_EINVAL before any HIP call): bad sizes, f < 1, ld < f, a null pointer with work to do.
+ *   ny == 0 returns DC_OK at once; cap == 0 writes the zero counts where counts is given and returns DC_OK; with
+ *   nx == 0 every count is 0.
+ *   DC_NEIGHBORS_ND_CHUNK: the columns the kernel stages per pass over a candidate tile (widths below, at and above
+ *   it and its multiples take different code paths: the tests read it). */
+#define DC_NEIGHBORS_ND_CHUNK 32
+int dc_neighbors_nd_fill(const float *x, int64_t ldx, int64_t nx, const int64_t *batch_x, const float *y, int64_t ldy,
+                         int64_t ny, const int64_t *batch_y, int64_t f, int cap, int exclude_self, int32_t *nbr,
+                         int32_t *counts, dc_stream_t stream);
+
 /* Order-dependent 64-bit content hash of an int64 device array (e.g. edge_index) into
  * out[1] (device): the key of the host's per-topology cache (loaders.TopologyCache), so a batch
  * whose edge_index has been seen before reuses its sorted adjacency. */

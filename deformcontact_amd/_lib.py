@@ -56,6 +56,8 @@ _SIGNATURES = {
     "dc_gat_alpha_bwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, _vp, c_int64, _vp, _vp,
                                  c_int, _vp]),
     "dc_spmm_f32_pack": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, c_int64, _vp]),
+    "dc_spmm_f32_pack_wprep": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                       POINTER(_vp), c_int, _vp, _vp]),
     "dc_spmm_f32_window": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
                                    c_int64, c_int64, _vp]),
     "dc_spmm_f32_rowmax_window": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
@@ -149,6 +151,8 @@ _SIGNATURES = {
     "dc_tag_linear_fwd_narrow_ok": (c_int, [c_int64, c_int, c_int64, c_int64]),
     "dc_tag_linear_fwd_narrow": (c_int, [_vp, c_int64, POINTER(_vp), c_int, c_int64, _vp, c_int, _vp, c_int64, c_int64,
                                          c_int64, c_int64, _vp]),
+    "dc_tag_narrow_wimage": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp]),
+    "dc_tag_linear_fwd_narrow_img": (c_int, [_vp, c_int64, _vp, _vp, c_int, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
     "dc_attn_softmax_rows": (c_int, [_vp, c_int64, c_int64, c_int64, c_int64, _vp, _vp]),
     "dc_attn_exp_rows": (c_int, [_vp, c_int64, c_int64, c_int64, c_int64, _vp, _vp]),
     "dc_attn_ds_rows": (c_int, [_vp, _vp, c_int64, c_int64, c_int64, _vp, _vp, _vp]),

@@ -22,7 +22,12 @@
 //   * epilogue through LDS: bias + ReLU in registers, accumulators into a [rows][256] fp32 image, one barrier, one 1-KiB row per
 //     global_store_dwordx4 wave-instruction (the 4-byte stores of the accumulator layout cost 7.6 us per 33.5 MB).
 // Bytes per launch (B = 32): 12.6 + 33.5 MB soft, 10.9 + 25.0 MB rigid; MFMA work 9.7 / 8.4 GFLOP: HBM-bound.
+//
+// Two forms of the first bullet.  k_fwd_narrow prepares the weights itself, in every workgroup, as described there (one
+// workgroup per CU: the fp32 LDS image).  k_fwd_narrow_img - what the layer runs - takes them prepared once per call
+// (dc_narrow_image.h) and runs two workgroups per CU: 16.3 / 14.9 us against 24.3 / 23.5 us (profiles/r11).
 #include "dc_dense.h"
+#include "dc_narrow_image.h"
 
 // timing-only ablations (tools/r06/narrow_abl.sh builds this file with -DDC_NARROW_ABL=<bits>; results are wrong by
 // construction): 1 no MFMAs, 2 no weight image (fragments made up), 4 no row stores, 8 no row loads / plane image, 16 no
@@ -44,53 +49,22 @@ struct NarrowParams {
     int relu, ntiles;
 };
 
-constexpr int kNarrowFo = 256;
-
 // The two barriers per tile are lds_barrier(), NOT __syncthreads(): its fence waits for vmcnt(0) - for the next tile's rows
 // (issued one tile ahead on purpose) and for the previous tile's 64 KB of row stores - which put two memory round trips per
 // tile on the critical path (30 us per launch instead of 12)
 
-// KS: k-steps of 16 (Kp = 16 KS); MB: 32-row blocks per tile
-template <int KS, int MB>
-__global__ void __launch_bounds__(256)
-k_fwd_narrow(NarrowParams p) {
-    constexpr int TR = 32 * MB;                         // rows per tile
-    constexpr int SROWA = KS * 96 + 16;                 // bytes per row of the plane image: [ks][plane][half][8 bf16] + pad
-    constexpr int PPR = 4 * KS;                         // float4 pieces per row
-    constexpr int TP = TR * PPR, NV = (TP + 255) / 256;
-    constexpr int KP = 16 * KS;                         // padded reduction
-    constexpr int kOffStage = ((TR * SROWA + 1023) / 1024) * 1024;
-    constexpr int kLdsTiles = kOffStage + TR * 1024, kLdsW = kNarrowFo * (KP + 4) * 4;      // tile images / prologue weight image
-    __shared__ __attribute__((aligned(1024))) char lds[kLdsTiles > kLdsW ? kLdsTiles : kLdsW];
-    char *const sA = lds;
-    float *const so = reinterpret_cast<float *>(lds + kOffStage);
+// The block's own weight prologue (k_fwd_narrow: the weights as the K + 1 lins[k].weight matrices) -> fb, this wave's
+// fragments.
+// First Wcat = [W_0 | ... | W_{nseg-1} | 0] as an fp32 image [256][Kp] in LDS, gathered with COALESCED reads of the
+// lins[k].weight matrices (element e of segment s = row e / fi, column e % fi; a per-lane gather of the fragments straight
+// from memory - 8 strided 4-byte loads per fragment - cost 20 us per launch: every workgroup made 7 M cache-line requests);
+// then every lane picks its fragments out of the image: column 64 wid + 32 nb + c, k = 16 ks + 8 h .. + 7.
+template <int KS>
+__device__ __forceinline__ void narrow_self_weights(const NarrowParams &p, char *lds, bf16x8 (&fb)[2][KS][3]) {
+    constexpr int KP = 16 * KS;
+    constexpr int WROW = KP + 4;                        // image row in floats: +16 B keeps the fragment picks conflict-free
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int c = lane & 31, h = lane >> 5;
-
-    // ---- x tile staging: piece q = threadIdx.x + 256 j of the tile = float4 c4 of row r ----
-    f32x4 xv[NV];
-    auto load_tile = [&](int t) {
-        const int64_t row0 = (int64_t)t * TR;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int q = (int)threadIdx.x + 256 * j;
-            if (TP % 256 != 0 && q >= TP) continue;
-            const int r = q / PPR, c4 = q - r * PPR;
-            int64_t row = row0 + r;
-            row = row < p.N ? row : p.N - 1;
-            if (DC_NARROW_ABL & 8) xv[j] = f32x4{(float)row, 1.f, 2.f, 3.f};
-            else xv[j] = *reinterpret_cast<const f32x4 *>(p.x + row * p.ld + 4 * c4);
-        }
-    };
-    int t = blockIdx.x;
-    if (t < p.ntiles) load_tile(t);                     // the first tile's rows travel while the weights are prepared
-
-    // ---- this wave's slice of the weights: fragments of all k-steps, three planes, in registers for the whole launch ----
-    // First Wcat = [W_0 | ... | W_{nseg-1} | 0] as an fp32 image [256][Kp] in LDS, gathered with COALESCED reads of the
-    // lins[k].weight matrices (element e of segment s = row e / fi, column e % fi; a per-lane gather of the fragments straight
-    // from memory - 8 strided 4-byte loads per fragment - cost 20 us per launch: every workgroup made 7 M cache-line requests);
-    // then every lane picks its fragments out of the image: column 64 wid + 32 nb + c, k = 16 ks + 8 h .. + 7.
-    constexpr int WROW = KP + 4;                        // image row in floats: +16 B keeps the fragment picks conflict-free
     {
         // ALL loads (every segment) are issued before the first is used: a load per loop trip waited for each one in turn
         // (84 round trips to L2, 25 us per launch); a batch per segment still made four round trips
@@ -126,7 +100,6 @@ k_fwd_narrow(NarrowParams p) {
         }
     }
     __syncthreads();
-    bf16x8 fb[2][KS][3];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
         const float *wr = reinterpret_cast<const float *>(lds) + (64 * wid + 32 * nb + c) * WROW + 8 * h;
@@ -143,6 +116,71 @@ k_fwd_narrow(NarrowParams p) {
         }
     }
     __syncthreads();                                    // the image's LDS becomes the plane / staging images
+}
+
+// The block, in both forms.  KS: k-steps of 16 (Kp = 16 KS); MB: 32-row blocks per tile.
+// WIMG: the weights come PREPARED - `img`, the bf16x3 fragment image of dc_narrow_image.h, written once per call by the
+// layer's pack launch (or k_narrow_wimage below) - instead of being prepared by every one of the 256 workgroups (all K + 1
+// weight matrices into a 102 KB fp32 LDS image, fragments picked, split1 on 256 x Kp numbers: 3.8 + ~2 us of a 23 us
+// launch).  The prologue is then 2 KS 3 coalesced 1-KiB wave loads from L2, issued behind the first tile's rows and
+// before anything is used: no LDS image, no barrier, and LDS is the tile images alone (52 / 55 / 58 KB) - TWO workgroups
+// fit a CU (256 registers per lane) and one's loads, split and row stores run under the other's MFMAs.  Same tiles,
+// k-step order, product order, bias, ReLU: the same bits.
+// LATE: the next tile's rows are asked for BEHIND the MFMAs (they then travel under the other workgroup's): with seven
+// k-steps their 16 registers beside 168 of fragments, 32 of accumulators and 12 of A fragments do not fit 256 (18 spilled).
+template <int KS, int MB, bool WIMG, bool LATE>
+__device__ __forceinline__ void narrow_block(const NarrowParams &p, const bf16x8 *__restrict__ img) {
+    constexpr int TR = 32 * MB;                         // rows per tile
+    constexpr int SROWA = KS * 96 + 16;                 // bytes per row of the plane image: [ks][plane][half][8 bf16] + pad
+    constexpr int PPR = 4 * KS;                         // float4 pieces per row
+    constexpr int TP = TR * PPR, NV = (TP + 255) / 256;
+    constexpr int KP = 16 * KS;                         // padded reduction
+    constexpr int kOffStage = ((TR * SROWA + 1023) / 1024) * 1024;
+    constexpr int kLdsTiles = kOffStage + TR * 1024, kLdsW = kNarrowFo * (KP + 4) * 4;      // tile images / prologue weight image
+    __shared__ __attribute__((aligned(1024))) char lds[(WIMG || kLdsTiles > kLdsW) ? kLdsTiles : kLdsW];
+    char *const sA = lds;
+    float *const so = reinterpret_cast<float *>(lds + kOffStage);
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int c = lane & 31, h = lane >> 5;
+
+    // ---- x tile staging: piece q = threadIdx.x + 256 j of the tile = float4 c4 of row r ----
+    f32x4 xv[NV];
+    auto load_tile = [&](int t) {
+        const int64_t row0 = (int64_t)t * TR;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int q = (int)threadIdx.x + 256 * j;
+            if (TP % 256 != 0 && q >= TP) continue;
+            const int r = q / PPR, c4 = q - r * PPR;
+            int64_t row = row0 + r;
+            row = row < p.N ? row : p.N - 1;
+            if (DC_NARROW_ABL & 8) xv[j] = f32x4{(float)row, 1.f, 2.f, 3.f};
+            else xv[j] = *reinterpret_cast<const f32x4 *>(p.x + row * p.ld + 4 * c4);
+        }
+    };
+    int t = blockIdx.x;
+    if (t < p.ntiles) load_tile(t);                     // the first tile's rows travel while the weights are prepared
+
+    // ---- this wave's slice of the weights: fragments of all k-steps, three planes, in registers for the whole launch ----
+    bf16x8 fb[2][KS][3];
+    if constexpr (WIMG) {
+        // columns [64 wid, 64 wid + 64) = column blocks 2 wid, 2 wid + 1 of the image
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+                for (int nb = 0; nb < 2; ++nb) {
+                    if (DC_NARROW_ABL & 2) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) fb[nb][ks][pl][j] = (__bf16)(float)(lane + ks + pl + nb);
+                    } else {
+                        fb[nb][ks][pl] = img[((ks * 3 + pl) * 8 + 2 * wid + nb) * 64 + lane];
+                    }
+                }
+    } else {
+        narrow_self_weights<KS>(p, lds, fb);
+    }
     float bcol[2];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) bcol[nb] = p.bias ? p.bias[64 * wid + 32 * nb + c] : 0.f;
@@ -187,7 +225,7 @@ k_fwd_narrow(NarrowParams p) {
         const int64_t row0 = (int64_t)t * TR;
         if (!(DC_NARROW_ABL & 8)) store_tile();         // (every wave is past the MFMAs of the previous tile: barrier B)
         if (prev_row0 >= 0) store_rows(prev_row0);
-        if (t + (int)gridDim.x < p.ntiles) load_tile(t + gridDim.x);
+        if (!LATE && t + (int)gridDim.x < p.ntiles) load_tile(t + gridDim.x);
         lds_barrier();                               // A: the plane image is complete; the staging image has been read
         f32x16 acc[MB][2];
 #pragma unroll
@@ -217,6 +255,7 @@ k_fwd_narrow(NarrowParams p) {
                         else
                             acc[mb][nb][tt] += (float)fa[mb][pa6[tt]][0] * (float)fb[nb][ks][pb6[tt]][0];
         }
+        if (LATE && t + (int)gridDim.x < p.ntiles) load_tile(t + gridDim.x);
         // epilogue: bias + ReLU, accumulators -> [TR][256] image (C/D layout: row (reg & 3) + 8 (reg >> 2) + 4 h, column c)
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
@@ -233,6 +272,34 @@ k_fwd_narrow(NarrowParams p) {
         prev_row0 = row0;
     }
     if (prev_row0 >= 0) store_rows(prev_row0);
+}
+
+template <int KS, int MB>
+__global__ void __launch_bounds__(256) k_fwd_narrow(NarrowParams p) { narrow_block<KS, MB, false, false>(p, nullptr); }
+
+// WPC: workgroups per CU the register budget is for
+template <int KS, int WPC>
+__global__ void __launch_bounds__(256, WPC) k_fwd_narrow_img(NarrowParams p, const bf16x8 *__restrict__ img) {
+    narrow_block<KS, 1, true, (WPC == 2 && KS > 6)>(p, img);
+}
+
+// the image on its own: calls in which no pack launch happens (cached hop slab, a caller's own slab)
+__global__ void __launch_bounds__(256) k_narrow_wimage(NarrowImageParams q) { narrow_image_fill(q, (int)blockIdx.x); }
+
+// workgroups per CU of k_fwd_narrow_img: two where 256 registers hold the fragments (wpad 96 / 112); DC_NARROW_WPC=1
+// keeps the grid at one per CU (measurements)
+static int narrow_wpc() {
+    static const int v = env_int("DC_NARROW_WPC", 2) == 1 ? 1 : 2;
+    return v;
+}
+
+template <int KS, int WPC>
+static void narrow_img_launch(const NarrowParams &p0, const void *img, hipStream_t hs) {
+    NarrowParams p = p0;
+    p.ntiles = (int)((p.N + 31) / 32);
+    const int cap = 256 * (WPC == 2 ? narrow_wpc() : 1);
+    const unsigned grid = (unsigned)(p.ntiles < cap ? p.ntiles : cap);
+    DC_LAUNCH((k_fwd_narrow_img<KS, WPC>), dim3(grid), dim3(256), 0, hs, p, static_cast<const bf16x8 *>(img));
 }
 
 // 32-row tiles: four (soft) / three (rigid) per persistent workgroup at B = 32 - measured 23.1 / 20.8 us against 25.1 / 22.6 us with
@@ -271,6 +338,8 @@ extern "C" int dc_tag_linear_fwd_narrow(const float *slab, int64_t ld, const flo
     p.x = slab, p.ld = ld, p.nseg = nseg, p.fi = (int)fi, p.bias = bias, p.out = out, p.ldo = ldo, p.N = N, p.relu = relu;
     for (int s = 0; s < nseg; ++s) {
         DC_REQUIRE(ws[s], "dc_tag_linear_fwd_narrow: null weight segment %d", s);
+        // (this kernel's prologue reads the weights 16 bytes at a time; dc_tag_linear_fwd_narrow_img takes any 4-byte address)
+        DC_REQUIRE(al16(ws[s]), "dc_tag_linear_fwd_narrow: weight segment %d is not 16-byte aligned", s);
         p.w[s] = ws[s];
     }
     hipStream_t hs = (hipStream_t)stream;
@@ -280,4 +349,38 @@ extern "C" int dc_tag_linear_fwd_narrow(const float *slab, int64_t ld, const flo
     default: narrow_launch<8>(p, hs); break;
     }
     return check_launch("dc_tag_linear_fwd_narrow");
+}
+
+extern "C" int dc_tag_narrow_wimage(const float *const *ws, int nseg, int64_t fi, int64_t wpad, void *wimg,
+                                    dc_stream_t stream) {
+    DC_REQUIRE(narrow_image_args_ok(ws, nseg, fi, wpad, wimg),
+               "dc_tag_narrow_wimage: needs 1..%d 4-byte-aligned weight segments [256, fi <= 32], a padded reduction of 96 / "
+               "112 / 128 >= nseg * fi and a 16-byte-aligned image (got nseg=%d fi=%lld wpad=%lld)", kMaxSeg, nseg,
+               (long long)fi, (long long)wpad);
+    const NarrowImageParams q = narrow_image_params(ws, nseg, fi, wpad, wimg);
+    DC_LAUNCH(k_narrow_wimage, dim3((unsigned)narrow_image_blocks(q.ks)), dim3(256), 0, (hipStream_t)stream, q);
+    return check_launch("dc_tag_narrow_wimage");
+}
+
+extern "C" int dc_tag_linear_fwd_narrow_img(const float *slab, int64_t ld, const void *wimg, const float *bias, int relu,
+                                            float *out, int64_t ldo, int64_t N, int64_t wpad, int64_t Fo,
+                                            dc_stream_t stream) {
+    DC_REQUIRE(Fo == kNarrowFo && (wpad == 96 || wpad == 112 || wpad == 128),
+               "dc_tag_linear_fwd_narrow_img: needs Fo = 256 and a padded reduction of 96 / 112 / 128 (got Fo=%lld wpad=%lld)",
+               (long long)Fo, (long long)wpad);
+    DC_REQUIRE(N >= 0, "dc_tag_linear_fwd_narrow_img: negative N");
+    if (N == 0) return DC_OK;
+    DC_REQUIRE(slab && wimg && out && ld >= wpad && ldo >= Fo, "dc_tag_linear_fwd_narrow_img: null pointer / short leading dimension");
+    DC_REQUIRE(ld % 4 == 0 && ldo % 4 == 0 && al16(slab) && al16(out) && al16(wimg),
+               "dc_tag_linear_fwd_narrow_img: rows of the slab and of the output and the image must be 16-byte aligned");
+    DC_REQUIRE(N < ((int64_t)1 << 31) - 64, "dc_tag_linear_fwd_narrow_img: too many rows");
+    NarrowParams p{};
+    p.x = slab, p.ld = ld, p.bias = bias, p.out = out, p.ldo = ldo, p.N = N, p.relu = relu;
+    hipStream_t hs = (hipStream_t)stream;
+    switch (wpad) {
+    case 96: narrow_img_launch<6, 2>(p, wimg, hs); break;
+    case 112: narrow_img_launch<7, 2>(p, wimg, hs); break;
+    default: narrow_img_launch<8, 1>(p, wimg, hs); break;
+    }
+    return check_launch("dc_tag_linear_fwd_narrow_img");
 }

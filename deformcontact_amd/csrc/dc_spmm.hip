@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "dc_common.h"
+#include "dc_narrow_image.h"
 
 #pragma clang fp contract(off)
 
@@ -190,15 +191,15 @@ __device__ __forceinline__ void chunk_ids(const int32_t *__restrict__ other, con
 }
 
 // ---- L lanes per row, 64/L rows per wave (narrow feature rows) -------------
+// the rows of logical block lb
 template <int VEC, int L, int U>
-__global__ void __launch_bounds__(256)
-k_spmm_sub(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
-           const float *__restrict__ w, const float *__restrict__ x, int64_t ldx,
-           const float *addend, int64_t ldadd, float *y, int64_t ldy,
-           int64_t N, int F, int src_off, float *self_dst = nullptr, int pad_beg = 0, int pad_end = 0) {
+__device__ __forceinline__ void
+spmm_sub_rows(unsigned lb, const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
+              const float *__restrict__ w, const float *__restrict__ x, int64_t ldx,
+              const float *addend, int64_t ldadd, float *y, int64_t ldy,
+              int64_t N, int F, int src_off, float *self_dst, int pad_beg, int pad_end) {
     using V = typename Vec<VEC>::T;
     constexpr int kRows = 256 / L;
-    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
     const int64_t row = (int64_t)lb * kRows + threadIdx.x / L;
     if (row >= N) return;
     const int sub = threadIdx.x % L;
@@ -243,6 +244,37 @@ k_spmm_sub(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
         }
         if (act) *reinterpret_cast<V *>(y + row * ldy + c) = acc;
     }
+}
+
+template <int VEC, int L, int U>
+__global__ void __launch_bounds__(256)
+k_spmm_sub(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
+           const float *__restrict__ w, const float *__restrict__ x, int64_t ldx,
+           const float *addend, int64_t ldadd, float *y, int64_t ldy,
+           int64_t N, int F, int src_off, float *self_dst = nullptr, int pad_beg = 0, int pad_end = 0) {
+    spmm_sub_rows<VEC, L, U>(xcd_remap(blockIdx.x, gridDim.x), ptr, other, w, x, ldx, addend, ldadd, y, ldy, N, F, src_off,
+                             self_dst, pad_beg, pad_end);
+}
+
+// The fused pack + first hop of a narrow first layer (dc_spmm_f32_pack) that also prepares the layer's weight image
+// for the short-reduction forward block (dc_narrow_image.h): narrow_image_blocks(ks) more workgroups in the same launch.
+// They are the FIRST hardware blocks, so among the first the dispatcher starts: their one round trip to the weights ends
+// long before the row blocks' tail does.  The row blocks behind them are remapped over the ROW grid alone - the chunks
+// of dc_spmm_f32_pack exactly (at B = 32 four whole meshes per XCD; remapped over the whole grid they straddled meshes
+// and the rigid launch took 10.7 instead of 10.1 us, profiles/r11); the shift only rotates which XCD serves which
+// chunk.  The image is read by a later launch on the same stream only.
+template <int L, int U>
+__global__ void __launch_bounds__(256)
+k_spmm_sub_wimg(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
+                const float *__restrict__ w, const float *__restrict__ x, int64_t ldx, float *y, int64_t ldy,
+                int64_t N, int F, float *self_dst, int pad_beg, int pad_end, NarrowImageParams img) {
+    const unsigned nimg = (unsigned)narrow_image_blocks(img.ks);
+    if (blockIdx.x < nimg) {
+        narrow_image_fill(img, (int)blockIdx.x);
+        return;
+    }
+    spmm_sub_rows<1, L, U>(xcd_remap(blockIdx.x - nimg, gridDim.x - nimg), ptr, other, w, x, ldx, nullptr, 0, y, ldy, N, F, 0,
+                           self_dst, pad_beg, pad_end);
 }
 
 template <int VEC, int L, int U>
@@ -624,6 +656,41 @@ extern "C" int dc_spmm_f32_pack(const int32_t *ptr, const int32_t *other, const 
     else
         launch_sub<1, 8, 8>(ptr, other, w, x, ldx, nullptr, 0, y, lds, N, (int)F, 0, stream, slab, (int)width, (int)wpad);
     return check_launch("dc_spmm_f32_pack");
+}
+
+template <int L>
+static void launch_pack_wimg(const int32_t *ptr, const int32_t *other, const float *w, const float *x, int64_t ldx,
+                             float *slab, int64_t lds, int64_t N, int F, int width, int wpad,
+                             const NarrowImageParams &img, hipStream_t stream) {
+    constexpr int kRows = 256 / L;
+    const unsigned grid = (unsigned)((N + kRows - 1) / kRows) + (unsigned)narrow_image_blocks(img.ks);
+    DC_LAUNCH((k_spmm_sub_wimg<L, 8>), dim3(grid), dim3(256), 0, stream, ptr, other, w, x, ldx, slab + F, lds, N, F, slab,
+              width, wpad, img);
+}
+
+// dc_spmm_f32_pack + the weight image of the layer's forward block in the same launch
+extern "C" int dc_spmm_f32_pack_wprep(const int32_t *ptr, const int32_t *other, const float *w, const float *x,
+                                      int64_t ldx, float *slab, int64_t lds, int64_t N, int64_t F, int64_t width,
+                                      int64_t wpad, const float *const *ws, int nseg, void *wimg, dc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DC_REQUIRE(N >= 1 && F >= 1 && F <= 32, "dc_spmm_f32_pack_wprep: at least one row of 1..32 floats (got N=%lld F=%lld)",
+               (long long)N, (long long)F);
+    DC_REQUIRE(ptr && x && slab, "dc_spmm_f32_pack_wprep: null pointer");
+    DC_REQUIRE(N < (int64_t)INT32_MAX / 8 && ldx >= F && width >= 2 * F && wpad >= width && lds >= wpad,
+               "dc_spmm_f32_pack_wprep: needs ldx >= F, width >= 2 F (block 1 exists), wpad >= width, lds >= wpad");
+    DC_REQUIRE((const void *)x != (const void *)slab, "dc_spmm_f32_pack_wprep: the slab must not alias x");
+    DC_REQUIRE(width == (int64_t)nseg * F && narrow_image_args_ok(ws, nseg, F, wpad, wimg),
+               "dc_spmm_f32_pack_wprep: needs 1..%d 4-byte-aligned weight segments with nseg * F = width, a padded width of "
+               "96 / 112 / 128 and a 16-byte-aligned image (got nseg=%d F=%lld width=%lld wpad=%lld)", kMaxSeg, nseg,
+               (long long)F, (long long)width, (long long)wpad);
+    const NarrowImageParams img = narrow_image_params(ws, nseg, F, wpad, wimg);
+    if (F > 16)
+        launch_pack_wimg<32>(ptr, other, w, x, ldx, slab, lds, N, (int)F, (int)width, (int)wpad, img, stream);
+    else if (F > 8)
+        launch_pack_wimg<16>(ptr, other, w, x, ldx, slab, lds, N, (int)F, (int)width, (int)wpad, img, stream);
+    else
+        launch_pack_wimg<8>(ptr, other, w, x, ldx, slab, lds, N, (int)F, (int)width, (int)wpad, img, stream);
+    return check_launch("dc_spmm_f32_pack_wprep");
 }
 
 extern "C" int dc_spmm_f32_window(const int32_t *ptr, const int32_t *other, const float *w,

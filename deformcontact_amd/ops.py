@@ -198,6 +198,33 @@ DENSE_PRODUCTS = 6
 #: ``dc_tag_linear_fwd_split``
 NARROW_FWD = os.environ.get("DC_NARROW_FWD", "1") != "0"
 
+#: that kernel on weights PREPARED once per call (``dc_tag_linear_fwd_narrow_img``): the bf16x3 fragment image of the
+#: layer's weights is written by the layer's own pack + first-hop launch (``dc_spmm_f32_pack_wprep``), or by
+#: ``dc_tag_narrow_wimage`` where the call has no such launch, instead of by every workgroup of the block; same bits.
+#: ``DC_NARROW_PREP=0``: the kernel that prepares its weights itself (``dc_tag_linear_fwd_narrow``).
+NARROW_PREP = os.environ.get("DC_NARROW_PREP", "1") != "0"
+
+
+class _NarrowImage:
+    """The weight image of a narrow layer's forward block: a temporary of ONE call (the weights change from step to
+    step, also under graph replay), like the outputs of ``_h2_weight_prep``.  ``filled``: a launch of this call has
+    written it already."""
+
+    STEP_BYTES = 3 * 8 * 64 * 16         # per 16 columns of the padded reduction (dc_narrow_image.h)
+
+    def __init__(self, ws, wpad: int, dev):
+        self.ws, self.wpad, self.filled = ws, wpad, False
+        self.buf = torch.empty(wpad // 16 * self.STEP_BYTES, dtype=torch.uint8, device=dev)
+
+    def ensure(self, st) -> int:
+        """Address of the image, written on stream ``st`` by a launch of its own if no other launch has."""
+        if not self.filled:
+            fi = self.ws[0].size(1)
+            _lib.check(_lib.lib().dc_tag_narrow_wimage(_ptr_array(self.ws), len(self.ws), fi, self.wpad,
+                                                       self.buf.data_ptr(), st), "dc_tag_narrow_wimage")
+            self.filled = True
+        return self.buf.data_ptr()
+
 #: fp16x2 mode of the wide (Fi % 16 == 0, unconcatenated) dense blocks: two power-of-two-scaled
 #: fp16 planes per operand and THREE MFMA products instead of the six of the bf16 split - still
 #: fp32-accurate (error below that of fp32 accumulation), half the matrix work.  The row maxima
@@ -326,9 +353,10 @@ def _hop_cache_put(g, key, x, slab, rowmax, dev):
 FUSED_PACK = os.environ.get("DC_FUSED_PACK", "1") != "0"
 
 
-def _build_input_slab(g: GraphIndex, x: torch.Tensor, k: int, want_rowmax: bool, into=None):
+def _build_input_slab(g: GraphIndex, x: torch.Tensor, k: int, want_rowmax: bool, into=None, nimg=None):
     """Pack ``x`` into block 0 of a ``[N, wpad]`` slab (fresh, or the buffers ``into`` = (slab,
-    rowmax) of an earlier call) and run the K hops (+ row maxima)."""
+    rowmax) of an earlier call) and run the K hops (+ row maxima).  ``nimg``: the ``_NarrowImage`` of the layer this
+    slab is for - the fused pack launch fills it on the side."""
     n, fi = x.shape
     concat, width, wpad = tag_slab_geometry(fi, k)
     dev = x.device
@@ -338,9 +366,14 @@ def _build_input_slab(g: GraphIndex, x: torch.Tensor, k: int, want_rowmax: bool,
     if (FUSED_PACK and adj is not None and not want_rowmax and fi <= 32 and not adj.row_offset and g.normalize
             and adj.ptr.numel() == n + 1):
         # the packing pass and the first hop in one launch (the chain of small dependent kernels a new batch starts with)
-        _lib.check(_lib.lib().dc_spmm_f32_pack(adj.ptr.data_ptr(), adj.other.data_ptr(), adj.w.data_ptr(),
-                                               xin.data_ptr(), xin.stride(0), slab.data_ptr(), slab.stride(0), n, fi,
-                                               width, wpad, current_stream_ptr(dev)), "dc_spmm_f32_pack")
+        args = (adj.ptr.data_ptr(), adj.other.data_ptr(), adj.w.data_ptr(), xin.data_ptr(), xin.stride(0),
+                slab.data_ptr(), slab.stride(0), n, fi, width, wpad)
+        if nimg is not None and not nimg.filled and len(nimg.ws) == k + 1:
+            _lib.check(_lib.lib().dc_spmm_f32_pack_wprep(*args, _ptr_array(nimg.ws), k + 1, nimg.buf.data_ptr(),
+                                                         current_stream_ptr(dev)), "dc_spmm_f32_pack_wprep")
+            nimg.filled = True
+        else:
+            _lib.check(_lib.lib().dc_spmm_f32_pack(*args, current_stream_ptr(dev)), "dc_spmm_f32_pack")
         for j in range(1, k):
             hop(adj, slab[:, j * fi:(j + 1) * fi], out=slab[:, (j + 1) * fi:(j + 2) * fi], weighted=True)
         return slab, None
@@ -530,10 +563,10 @@ def _dense_operands(slab: torch.Tensor, fi: int, k: int, concat: bool):
     return [slab[:, j * fi:(j + 1) * fi] for j in range(k + 1)], [ld] * (k + 1), fi, k + 1
 
 
-def _tag_slab(g, x: torch.Tensor, weights, h2: bool, need_x: bool):
+def _tag_slab(g, x: torch.Tensor, weights, h2: bool, need_x: bool, nimg=None):
     """First step of a TAGConv layer's forward: the hop slab ``[x | A x | ... | A^K x]`` and, for the fp16x2 block
     (``h2``), its row maxima.  -> (slab, rowmax, prepped); ``prepped``: the layer's ``_h2_weight_prep`` where it had
-    to be launched here already, else None."""
+    to be launched here already, else None.  ``nimg``: the layer's ``_NarrowImage``, for the pack launch to fill."""
     n, fi = x.shape
     k = len(weights) - 1
     dev = x.device
@@ -551,7 +584,7 @@ def _tag_slab(g, x: torch.Tensor, weights, h2: bool, need_x: bool):
             if hit is not None:
                 slab, rowmax = hit
         if slab is None:
-            slab, rowmax = _build_input_slab(g, x, k, h2)
+            slab, rowmax = _build_input_slab(g, x, k, h2, nimg=nimg)
             if key is not None:
                 _hop_cache_put(g, key, x, slab, rowmax, dev)
     else:
@@ -752,9 +785,11 @@ class _TagConvFn(torch.autograd.Function):
         concat, width, wpad = tag_slab_geometry(fi, k)
         path = _dense_path(fi, k, fo, six, concat and bool(L.dc_tag_linear_fwd_narrow_ok(fi, k + 1, wpad, fo)))
         need_x = ctx.needs_input_grad[1]
-        slab, rowmax, prepped = _tag_slab(g, x, weights, path == "h2", need_x)
-        # the short-reduction kernel gathers its weight fragments from the lins[k].weight matrices themselves
+        # the short-reduction kernel takes the lins[k].weight matrices themselves: their fragment image is made once per
+        # call, by the pack launch of _tag_slab where there is one
         ws = [w.contiguous() for w in weights]
+        nimg = _NarrowImage(ws, wpad, dev) if (path == "narrow" and NARROW_PREP) else None
+        slab, rowmax, prepped = _tag_slab(g, x, weights, path == "h2", need_x, nimg)
         if concat and path != "narrow":
             ws = [_pack_weights(ws, fo, fi, wpad, st)]
         out = _tag_out_buffer(next_geom, n, fo, dev)
@@ -772,6 +807,9 @@ class _TagConvFn(torch.autograd.Function):
             rc = L.dc_tag_linear_fwd_h2p(slab.data_ptr(), slab.stride(0), wimg.data_ptr(), _ptr(b), int(relu),
                                          out.data_ptr(), ldo, n, width, fo, rowmax.data_ptr(), wmax.data_ptr(),
                                          None, 0, st)
+        elif path == "narrow" and nimg is not None:
+            rc = L.dc_tag_linear_fwd_narrow_img(slab.data_ptr(), slab.stride(0), nimg.ensure(st), _ptr(b), int(relu),
+                                                out.data_ptr(), ldo, n, wpad, fo, st)
         elif path == "narrow":
             rc = L.dc_tag_linear_fwd_narrow(slab.data_ptr(), slab.stride(0), _ptr_array(ws), k + 1, fi, _ptr(b),
                                             int(relu), out.data_ptr(), ldo, n, wpad, fo, st)

@@ -263,6 +263,11 @@ int dc_spmm_f32(const int32_t *ptr, const int32_t *other, const float *w, const 
 int dc_spmm_f32_pack(const int32_t *ptr, const int32_t *other, const float *w, const float *x, int64_t ldx,
                      float *slab, int64_t lds, int64_t N, int64_t F, int64_t width, int64_t wpad,
                      dc_stream_t stream);
+/* ... and, in the same launch, the weight image of the layer's forward block (dc_tag_narrow_wimage below: ws, nseg with
+ * nseg * F = width, wimg; wpad = 96 / 112 / 128): a few more workgroups prepare it once per call. */
+int dc_spmm_f32_pack_wprep(const int32_t *ptr, const int32_t *other, const float *w, const float *x, int64_t ldx,
+                           float *slab, int64_t lds, int64_t N, int64_t F, int64_t width, int64_t wpad,
+                           const float *const *ws, int nseg, void *wimg, dc_stream_t stream);
 
 /* dc_spmm_f32 over a ROW WINDOW of a merged adjacency (dc_graph_build_parts): `ptr` points at the
  * window's first row (N + 1 entries; its values index the full other / w arrays), neighbour ids are
@@ -422,6 +427,15 @@ int dc_tag_linear_fwd_narrow_ok(int64_t fi, int nseg, int64_t wpad, int64_t Fo);
 int dc_tag_linear_fwd_narrow(const float *slab, int64_t ld, const float *const *ws, int nseg, int64_t fi,
                              const float *bias, int relu, float *out, int64_t ldo, int64_t N, int64_t wpad,
                              int64_t Fo, dc_stream_t stream);
+/* The same block on PREPARED weights.  dc_tag_narrow_wimage: wimg (wpad / 16 * 24576 bytes, 16-byte aligned) = the three
+ * bf16 planes (hi, mid, lo: round-to-nearest-even of x, x - hi, x - hi - mid) of [W_0 | ... | W_{nseg-1} | 0] in the order
+ * the kernel's lanes hold them: [wpad / 16 k-steps][3 planes][8 column blocks of 32][64 lanes][8 bf16], record
+ * (ks, plane, block, lane = c + 32 h) = columns k = 16 ks + 8 h .. + 7 of output column 32 block + c.  ws[k] may sit at
+ * any 4-byte-aligned address.  dc_tag_linear_fwd_narrow_img: the forward block reading that image - no weight prologue
+ * per workgroup, two workgroups per CU for wpad = 96 / 112; outputs bit-identical to dc_tag_linear_fwd_narrow. */
+int dc_tag_narrow_wimage(const float *const *ws, int nseg, int64_t fi, int64_t wpad, void *wimg, dc_stream_t stream);
+int dc_tag_linear_fwd_narrow_img(const float *slab, int64_t ld, const void *wimg, const float *bias, int relu,
+                                 float *out, int64_t ldo, int64_t N, int64_t wpad, int64_t Fo, dc_stream_t stream);
 int64_t dc_tag_linear_bwd_dx_split_workspace_bytes(int64_t Fi, int64_t Fo, int nseg);
 int dc_tag_linear_bwd_dx_split(const float *g, int64_t ldg, const float *out_for_mask,
                                int64_t ldo, const float *const *ws, int nseg, float *const *gxs,

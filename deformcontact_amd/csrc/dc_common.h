@@ -50,6 +50,22 @@ __device__ __forceinline__ float inv_sqrt_count(int d) {
     return d > 0 ? 1.0f / sqrtf((float)d) : 0.0f;
 }
 
+// ReLU of every fused epilogue, torch.threshold's semantics: NaN stays NaN (fmaxf(NaN, 0) is 0 and would hide a
+// diverged run), -0.0 -> +0.  ONE definition.  IEEE 754-2019 maximum, which propagates NaN and
+// orders -0 below +0: one v_maximum3_f32 on gfx950, where `v <= 0.f ? 0.f : v` is a compare and a select
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
+// one step of the max aggregations' walk (SAGE, EdgeConv / PointNetConv, global_max_pool): the running maximum mx and
+// the number ct of candidates that attain it take in n candidates of value a (n > 1: a merged partial result).  Greater:
+// the maximum is replaced and the count starts again; equal: n more.  A NaN candidate wins and then stays (NaN > x is
+// false for every x), as in torch's scatter_reduce(..., 'amax'); the count of a NaN maximum is the number of NaN
+// candidates.  +-Inf are ordinary values: the maximum is a selection
+__device__ __forceinline__ void max_step(float a, int n, float &mx, int &ct) {
+    const bool a_nan = a != a, take = a > mx || a_nan;
+    ct = mx != mx ? (a_nan ? ct + n : ct) : (take ? n : (a == mx ? ct + n : ct));
+    mx = take ? a : mx;
+}
+
 // ---- primitives with users outside the dense family (dc_spmm.hip, dc_hopchain.hip, dc_attn.hip); the dense
 // kernels' own are in dc_dense.h ----
 using f32x4 = __attribute__((ext_vector_type(4))) float;

@@ -144,7 +144,7 @@ k_fwd_bf16(Bf16Params p) {
         const int64_t row = row0 + rr, col = col0 + c;
         if (row < p.N && col < p.Fo) {
             v += bcol[(c >> 5) & 1];
-            if (relu) v = fmaxf(v, 0.f);
+            if (relu) v = relu_keep_nan(v);
             if (p.out_bf16) ((uint16_t *)p.out)[row * p.ldo + col] = f32_to_bf16_rne(v);
             else ((float *)p.out)[row * p.ldo + col] = v;
         }
@@ -286,7 +286,7 @@ k_fwd_bf16x(Bf16Params p) {
                     for (int reg = 0; reg < 16; ++reg) {
                         const int rl = rbase + mb * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
                         float v = acc[mb][nb][reg] + bcol;
-                        if (relu) v = fmaxf(v, 0.f);
+                        if (relu) v = relu_keep_nan(v);
                         if (OUT_BF16) *reinterpret_cast<uint16_t *>(dst + rl * rs) = f32_to_bf16_rne(v);
                         else *reinterpret_cast<float *>(dst + rl * rs) = v;
                     }

@@ -170,7 +170,7 @@ k_fwd_fast(FwdParams p) {
         const int64_t row = row0 + r, col = col0 + c;
         if (row < p.N && col < p.Fo) {
             v += bcol[(c >> 5) & 1];
-            if (relu) v = fmaxf(v, 0.f);
+            if (relu) v = relu_keep_nan(v);
             p.out[row * p.ldo + col] = v;
         }
     });

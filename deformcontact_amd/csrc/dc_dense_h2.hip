@@ -225,7 +225,7 @@ k_fwd_h2(FwdParams p) {
         if (row < p.N && col < p.Fo) {
             v = (v * s_inv[rr]) * icol[(c >> 5) & 1];
             v += bcol[(c >> 5) & 1];
-            if (relu) v = fmaxf(v, 0.f);
+            if (relu) v = relu_keep_nan(v);
             if (p.exp_lse) v = col < p.exp_ncols ? expf(v - p.exp_lse[row]) : 0.f;
             p.out[row * p.ldo + col] = v;
         }

@@ -77,7 +77,7 @@ k_fwd_h2d(FwdParams p) {
             for (int i = 0; i < 4; ++i) {
                 float t = (v[i] * sv) * icol[i];
                 t += bcol[i];
-                if (relu) t = fmaxf(t, 0.f);
+                if (relu) t = relu_keep_nan(t);
                 v[i] = row >= data_end ? 0.f : t;             // padding rows of a grouped launch stay zero rows
             }
             if (FULL || (row < p.N && col < p.Fo)) *reinterpret_cast<f32x4 *>(p.out + row * p.ldo + col) = v;

@@ -279,7 +279,7 @@ k_fwd_h2w(FwdParams p) {
                     const int64_t row = row0 + rl + i;
                     float v = (acc[mb][nb][4 * g + i] * sv[i]) * icol;
                     v += bcol;
-                    if (relu) v = fmaxf(v, 0.f);
+                    if (relu) v = relu_keep_nan(v);
                     if (p.exp_lse)                  // attention recompute: the block's weights from the saved row lse
                         v = col < p.exp_ncols ? expf(v - p.exp_lse[(FULL || row < p.N) ? row : p.N - 1]) : 0.f;
                     if (row >= data_end) v = 0.f;            // padding rows of a grouped launch stay zero rows

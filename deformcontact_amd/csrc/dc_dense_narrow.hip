@@ -264,7 +264,7 @@ __device__ __forceinline__ void narrow_block(const NarrowParams &p, const bf16x8
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     float v = acc[mb][nb][r] + bcol[nb];
-                    if (relu) v = fmaxf(v, 0.f);
+                    if (relu) v = relu_keep_nan(v);
                     if (!(DC_NARROW_ABL & 16) || r == 0)
                         so[(mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 256 + 64 * wid + 32 * nb + c] = v;
                 }

@@ -270,7 +270,7 @@ k_fwd_split(FwdParams p) {
         if (row < p.N && col < p.Fo) {
             if (F16) v = (v * s_inv[r]) * icol[(c >> 5) & 1];
             v += bcol[(c >> 5) & 1];
-            if (relu) v = fmaxf(v, 0.f);
+            if (relu) v = relu_keep_nan(v);
             p.out[row * p.ldo + col] = v;
         }
     });

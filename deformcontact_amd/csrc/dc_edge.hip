@@ -20,8 +20,8 @@
 //                    mean  g_m[q,c] = g_y[dst_q,c] / float(deg_{dst_q})
 //                    max   g_m[q,c] = (m[q,c] == y[dst_q,c]) ? g_y[dst_q,c] / float(cnt[dst_q,c]) : 0
 // The max backward splits the gradient EVENLY among all edges that attain the maximum, a duplicate edge counting as an
-// edge; the comparison is exact - y is a copy of one of the reduced values.  Inputs are taken to be finite, as in
-// dc_sage.hip.
+// edge; the comparison is exact - y is a copy of one of the reduced values.  Non-finite inputs as in dc_sage.hip
+// (INTEGRATION.md 1.14): contained sums, a NaN-propagating max forward (max_step) that selects among +-Inf exactly.
 //
 // The two kernels with one lane group per INPUT edge q (pair forward, reduce backward) stream their edge rows - row q
 // in, row q out, every output row written exactly once by one lane group - and gather only node rows (x[src_q],
@@ -200,11 +200,7 @@ k_edge_max_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ perm
             for (int u = 0; u < U; ++u)
                 if (u < n) {
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) {
-                        const float a = v[u].a[k];
-                        ct[k] = a > mx[k] ? 1 : (a == mx[k] ? ct[k] + 1 : ct[k]);
-                        mx[k] = a > mx[k] ? a : mx[k];
-                    }
+                    for (int k = 0; k < VEC; ++k) max_step(v[u].a[k], 1, mx[k], ct[k]);
                 }
         }
         if (end <= beg) {

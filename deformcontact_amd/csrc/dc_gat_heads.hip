@@ -139,8 +139,8 @@ __device__ __forceinline__ void hadd(float &a, float b) { a = a + b; }
 __device__ __forceinline__ void hadd(float4 &a, const float4 &b) { a.x = a.x + b.x, a.y = a.y + b.y, a.z = a.z + b.z, a.w = a.w + b.w; }
 __device__ __forceinline__ void hdiv(float &a, float d) { a = a / d; }
 __device__ __forceinline__ void hdiv(float4 &a, float d) { a.x = a.x / d, a.y = a.y / d, a.z = a.z / d, a.w = a.w / d; }
-__device__ __forceinline__ void hrelu(float &a) { a = fmaxf(a, 0.f); }
-__device__ __forceinline__ void hrelu(float4 &a) { a.x = fmaxf(a.x, 0.f), a.y = fmaxf(a.y, 0.f), a.z = fmaxf(a.z, 0.f), a.w = fmaxf(a.w, 0.f); }
+__device__ __forceinline__ void hrelu(float &a) { a = relu_keep_nan(a); }
+__device__ __forceinline__ void hrelu(float4 &a) { a.x = relu_keep_nan(a.x), a.y = relu_keep_nan(a.y), a.z = relu_keep_nan(a.z), a.w = relu_keep_nan(a.w); }
 
 // y[row, c] = act(sum_p alpha[p, c / C] x[other[p], c] + bias[c]) over the H*C columns (MEAN: the C columns of
 // (1/H) sum_k sum_p alpha[p, k] x[other[p], k C + c]).  The row index, segment bounds and neighbour ids are

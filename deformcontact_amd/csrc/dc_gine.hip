@@ -73,7 +73,7 @@ k_gine_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other, c
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) {
                         const float m = xv[u].a[k] + ev[u].a[k];
-                        acc[k] = acc[k] + (m > 0.f ? m : 0.f);
+                        acc[k] = acc[k] + relu_keep_nan(m);
                     }
                 }
         }

@@ -31,7 +31,8 @@ k_loss_nodes(const int32_t *__restrict__ ptr_f, const int32_t *__restrict__ oth_
         const V3 p = ld3(pred, ldp, i), t = ld3(tgt, ldt, i);
         const float dx = p.x - t.x, dy = p.y - t.y, dz = p.z - t.z;
         s_l1 = fabsf(dx) + fabsf(dy) + fabsf(dz);
-        auto sgn = [](float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); };
+        // torch.sign: a NaN difference keeps its NaN in the gradient, a zero one gives 0
+        auto sgn = [](float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : (v != v ? v : 0.f)); };
         g_l1[i * 3] = sgn(dx) * inv_3n;
         g_l1[i * 3 + 1] = sgn(dy) * inv_3n;
         g_l1[i * 3 + 2] = sgn(dz) * inv_3n;
@@ -45,7 +46,7 @@ k_loss_nodes(const int32_t *__restrict__ ptr_f, const int32_t *__restrict__ oth_
                         ez = (t.z - ts.z) - (p.z - ps.z);
             const float nrm = sqrtf(ex * ex + ey * ey + ez * ez);
             gc += (double)nrm;
-            const float r = nrm > 0.f ? 1.f / nrm : 0.f;      // torch: zero gradient at a zero norm
+            const float r = nrm > 0.f ? 1.f / nrm : (nrm != nrm ? nrm : 0.f);  // torch: zero gradient at a zero norm, NaN at a NaN one
             gx -= ex * r, gy -= ey * r, gz -= ez * r;
         }
         // out-edges i -> dst:  d = (t_dst - t_i) - (p_dst - p_i);  d loss / d p_i = +d / |d|
@@ -55,7 +56,7 @@ k_loss_nodes(const int32_t *__restrict__ ptr_f, const int32_t *__restrict__ oth_
             const float ex = (td.x - t.x) - (pd.x - p.x), ey = (td.y - t.y) - (pd.y - p.y),
                         ez = (td.z - t.z) - (pd.z - p.z);
             const float nrm = sqrtf(ex * ex + ey * ey + ez * ez);
-            const float r = nrm > 0.f ? 1.f / nrm : 0.f;
+            const float r = nrm > 0.f ? 1.f / nrm : (nrm != nrm ? nrm : 0.f);
             gx += ex * r, gy += ey * r, gz += ez * r;
         }
         s_gc = (float)gc;

@@ -40,7 +40,8 @@
 // Rules of the segment kernels (dc_segment.h, dc_edge.hip): fp contract(off), every sum in a fixed order, no float atomics,
 // no host read - two runs give the same bits and every entry can be captured.  Any width >= 1 (pair: F >= 0); 16-byte
 // accesses where the width % 4 == 0 and every pointer and stride allows it, scalar otherwise; the three position columns
-// are always scalar.  Lanes as in dc_edge.hip (seg_row).  Inputs are taken to be finite.
+// are always scalar.  Lanes as in dc_edge.hip (seg_row).  Non-finite features and pooled rows follow
+// INTEGRATION.md 1.14 (the pools' max walks with max_step: NaN propagates, +-Inf are ordinary values).
 #include "dc_segment.h"
 
 #pragma clang fp contract(off)
@@ -236,8 +237,7 @@ k_pool_fwd(const int64_t *__restrict__ ptr, const float *__restrict__ x, int64_t
                 for (int k = 0; k < VEC; ++k) {
                     const float e = v[u].a[k];
                     if (is_max) {
-                        ct[k] = e > acc[k] ? 1 : (e == acc[k] ? ct[k] + 1 : ct[k]);
-                        acc[k] = e > acc[k] ? e : acc[k];
+                        max_step(e, 1, acc[k], ct[k]);
                     } else {
                         acc[k] = acc[k] + e;
                     }
@@ -253,9 +253,7 @@ k_pool_fwd(const int64_t *__restrict__ ptr, const float *__restrict__ x, int64_t
         for (int k = 0; k < VEC; ++k) {
             const float e = s_v[s][sub * VEC + k];
             if (is_max) {
-                const int n = s_c[s][sub * VEC + k];
-                ct[k] = e > acc[k] ? n : (e == acc[k] ? ct[k] + n : ct[k]);
-                acc[k] = e > acc[k] ? e : acc[k];
+                max_step(e, s_c[s][sub * VEC + k], acc[k], ct[k]);
             } else {
                 acc[k] = acc[k] + e;
             }

@@ -9,8 +9,12 @@
 // A row without edges is 0 (m = 0, cnt = 0).  The sum is the plain fp32 sum of the unweighted hop (dc_spmm.hip: 1 * v
 // added in p order), so mean == hop / deg bit for bit; the division is a true (correctly rounded) division.  The max
 // backward splits the gradient EVENLY among all edges that attain the maximum, duplicates each counting as an edge;
-// the comparison is exact - m is a copy of one of the gathered values - so no index image is kept.  Inputs are taken
-// to be finite: what a NaN does to the maximum, its count and the split is unspecified.
+// the comparison is exact - m is a copy of one of the gathered values - so no index image is kept.  Non-finite
+// inputs (INTEGRATION.md "Non-finite values"): the maximum is a selection, so +-Inf candidates are ordinary values and the
+// forward equals scatter_reduce(..., 'amax') exactly; a NaN candidate makes m[i,c] NaN, as there, and cnt[i,c] the number
+// of NaN candidates (max_step, dc_common.h).  The sums and the mean carry NaN / Inf as fp32 addition does, into the
+// rows and columns that depend on them and no others.  The backward of a non-finite forward is not specified; on a finite
+// forward a non-finite g_m[i,c] reaches exactly the edges that attain m[i,c].
 //
 // Rules of the segment kernels (helpers: see dc_segment.h): every sum in a fixed order (the backward sums compensated), no
 // float atomics, no host read - two runs give the same bits.  Any F >= 1: 16-byte loads where F % 4 == 0 and every pointer
@@ -138,11 +142,7 @@ k_sage_max_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ othe
             for (int u = 0; u < U; ++u)
                 if (u < n) {
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) {
-                        const float a = v[u].a[k];
-                        ct[k] = a > mx[k] ? 1 : (a == mx[k] ? ct[k] + 1 : ct[k]);
-                        mx[k] = a > mx[k] ? a : mx[k];
-                    }
+                    for (int k = 0; k < VEC; ++k) max_step(v[u].a[k], 1, mx[k], ct[k]);
                 }
         }
         if (end <= beg) {

@@ -173,7 +173,7 @@ k_spline_fwd(const int32_t *__restrict__ ptr, const int32_t *__restrict__ other,
         }
         if (relu) {
 #pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[v] = acc[v] > 0.f ? acc[v] : 0.f;
+            for (int v = 0; v < VEC; ++v) acc[v] = relu_keep_nan(acc[v]);
         }
         cols_store<VEC>(y + row * ldy + c, acc);
     }

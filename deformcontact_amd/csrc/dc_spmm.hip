@@ -49,8 +49,8 @@ __device__ __forceinline__ void vaxpy(float4 &acc, float w, const float4 &v) {
 
 __device__ __forceinline__ void vadd(float &a, float b) { a = a + b; }
 __device__ __forceinline__ void vadd(float4 &a, const float4 &b) { a.x = a.x + b.x, a.y = a.y + b.y, a.z = a.z + b.z, a.w = a.w + b.w; }
-__device__ __forceinline__ void vrelu(float &a) { a = fmaxf(a, 0.f); }
-__device__ __forceinline__ void vrelu(float4 &a) { a.x = fmaxf(a.x, 0.f), a.y = fmaxf(a.y, 0.f), a.z = fmaxf(a.z, 0.f), a.w = fmaxf(a.w, 0.f); }
+__device__ __forceinline__ void vrelu(float &a) { a = relu_keep_nan(a); }
+__device__ __forceinline__ void vrelu(float4 &a) { a.x = relu_keep_nan(a.x), a.y = relu_keep_nan(a.y), a.z = relu_keep_nan(a.z), a.w = relu_keep_nan(a.w); }
 
 // ---- one wave per destination row (F >= 64*VEC/2 ... up to any F) ----------
 __device__ __forceinline__ float vabsmax(float v) { return fabsf(v); }

@@ -848,7 +848,10 @@ int dc_tconv_source_bwd(const int32_t *ptr_t, const int32_t *other_t, const int3
  * is given - no self loop is added, duplicates count, a row may have no edge - and their backward over the key_row=0
  * set (ptr_t / other_t = destination ids).  Any F >= 1 (no width cap), any in-degree >= 0, N = 0; 16-byte loads when
  * F % 4 == 0 and every pointer and row stride is 16-byte aligned.  Sums in a fixed order (the backward sums
- * compensated), no float atomics, no workspace: deterministic.  Inputs are finite; what a NaN does is unspecified.
+ * compensated), no float atomics, no workspace: deterministic.  Non-finite inputs: the
+ * sums carry NaN / Inf into the rows and columns that depend on them and no others; the max forward selects among +-Inf
+ * exactly and a NaN candidate makes m NaN with cnt = the number of NaN candidates; the backward of a non-finite forward
+ * is not specified.
  * Arguments are checked before any HIP call, in this order: sizes (N < 0, F < 1, range), leading dimensions, then
  * null pointers, then aliasing - DC_EINVAL with the entry's name in dc_last_error().  N == 0 returns DC_OK before the
  * null check (an empty tensor has no address).
@@ -906,7 +909,8 @@ int dc_gine_bwd_e(const int64_t *src, const int64_t *dst, const float *x, int64_
  * edge id of every sorted position) and the key_row=0 set (ptr_t / perm_t) are those of that edge list taken as it is
  * given - no self loop is added, duplicates count, a row may have no edge.  Any width >= 1 (no cap), any in-degree >= 0;
  * 16-byte loads when the width % 4 == 0 and every pointer and row stride is 16-byte aligned.  Sums in a fixed order, no
- * float atomics, no workspace, no host read: deterministic and capturable.  Inputs are taken to be finite.  Arguments
+ * float atomics, no workspace, no host read: deterministic and capturable.  Non-finite inputs as for the SAGE entries above
+ * (contained sums, a NaN-propagating max that selects among +-Inf exactly).  Arguments
  * are checked before any HIP call, in the order of the GINE entries: sizes and leading dimensions, then null pointers,
  * then aliasing.  A zero row count (E for the entries that walk the input edges, N for the others) returns DC_OK
  * before the null check.  mode: 0 sum, 1 mean, 2 max.
@@ -1052,7 +1056,8 @@ int dc_spline_bwd_a(const float *gb, const float *a, int64_t lda, const int64_t 
 
 /* ---- Point-set sampling and transfer (dc_pointops.hip; PyG fps, knn_interpolate) ----
  * Distances as in the neighbour search: d2 = ((dx*dx + dy*dy) + dz*dz) in fp32, each operation rounded on its own.
- * Fixed order, no float atomics, no host read: deterministic and capturable.  Inputs are taken to be finite.  Arguments
+ * Fixed order, no float atomics, no host read: deterministic and capturable.  Positions select indices: behaviour
+ * on non-finite input is unspecified here ("out of scope").  Arguments
  * are checked before any HIP call: sizes, leading dimensions, then null pointers, then aliasing.
  *   dc_fps : farthest point sampling of B graphs, one workgroup per graph.  x fp32 [N, >= 3] (leading dimension ldx).
  *            ptr int64 [B+1]: graph g owns the nodes [ptr[g], ptr[g+1]); optr int64 [B+1]: it writes the picks

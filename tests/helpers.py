@@ -113,3 +113,111 @@ def random_multigraph(n, e, seed, self_loops=True, isolated=True):
         if self_loops:
             src[8:12] = dst[8:12]
     return np.stack([src, dst]).astype(np.int64)
+
+
+# --------------------------------------------------------------------------- #
+# non-finite values (tests/test_nonfinite.py): ONE poison in clean finite inputs.  No tolerance:
+# every assertion is isfinite, a float64 equality or torch.equal on bits.
+# --------------------------------------------------------------------------- #
+#: the three poisons, NaN first (its float64 restatement defines the reach set)
+POISONS = (("nan", float("nan")), ("+inf", float("inf")), ("-inf", float("-inf")))
+
+
+def poisoned(inputs, name, index, value):
+    """A copy of the dict of tensors ``inputs`` with ``inputs[name][index] = value`` (``index``: a tuple; a whole row is
+    ``(r,)`` or ``(r, slice(None))``); the other tensors are shared, none is modified."""
+    out = dict(inputs)
+    t = inputs[name].clone()
+    t[index] = value
+    out[name] = t
+    return out
+
+
+def reach_sets(ref, inputs64, name, index, value=float("nan")):
+    """-> list of bool tensors, one per output of ``ref`` (a float64 restatement: dict of float64 CPU tensors -> list
+    of float64 tensors): where the restatement is NON-FINITE with ``value`` placed at ``inputs64[name][index]``.  With
+    the NaN poison this is the reach set R."""
+    outs = ref(poisoned(inputs64, name, index, value))
+    return [~torch.isfinite(o) for o in outs]
+
+
+def assert_not_swallowed(out, must, what=""):
+    """Rule 1: ``out`` (any device / float dtype) is non-finite at every position of the bool mask ``must``."""
+    bad = torch.isfinite(out.detach().cpu().float()) & must
+    assert not bool(bad.any()), (f"{what}: a non-finite value was swallowed at {int(bad.sum())} of {int(must.sum())} "
+                                 f"positions, first {tuple(int(v) for v in bad.nonzero()[0])}")
+
+
+def assert_contained(out, clean, reach, what=""):
+    """Rule 2: outside the reach set ``reach`` the output has the bits of the same kernel's output on the clean inputs."""
+    keep = ~reach
+    a, b = out.detach().cpu(), clean.detach().cpu()
+    assert a.shape == b.shape == keep.shape, (what, a.shape, b.shape, keep.shape)
+    a, b = a[keep], b[keep]
+    same = torch.equal(a, b) if a.dtype != torch.float32 else torch.equal(a.view(torch.int32), b.view(torch.int32))
+    if not same:
+        diff = (out.detach().cpu() != clean.detach().cpu()) & keep     # (a clean output is finite: != is a bit difference
+        raise AssertionError(f"{what}: {int(diff.sum())} positions outside the reach set changed, first "   # up to +-0)
+                             f"{tuple(int(v) for v in diff.nonzero()[0]) if diff.any() else 'a sign of zero'}")
+
+
+def assert_selection(out, ref64, what=""):
+    """Rule 3: the output equals the float64 restatement exactly, everywhere (+-Inf compare equal to themselves)."""
+    a = out.detach().cpu().double()
+    assert a.shape == ref64.shape, (what, a.shape, ref64.shape)
+    bad = ~((a == ref64) | (torch.isnan(a) & torch.isnan(ref64)))
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} positions differ from the float64 restatement"
+
+
+def graph_rows(edge_index, n):
+    """Rows the poison placements use: a MID row with in-edges and out-edges that is neither row 0 nor the last, and
+    the last row.  ``edge_index``: int array [2, E]."""
+    src, dst = np.asarray(edge_index[0]), np.asarray(edge_index[1])
+    both = sorted(set(src.tolist()) & set(dst.tolist()) - {0, n - 1})
+    mid = both[len(both) // 2] if both else 0
+    return mid, n - 1
+
+
+def element_placements(edge_index, n, f):
+    """The placements of a poison in a node-valued [n, f] input: element [0, 0] (padded lanes and tail iterations
+    conventionally read element 0: the containment probe), an element of a mid row with in- and out-edges, an
+    element of the last row, an element in the last column."""
+    mid, last = graph_rows(edge_index, n)
+    out = {"first": (0, 0), "mid": (mid, f // 2), "lastrow": (last, min(1, f - 1)), "lastcol": (mid // 2, f - 1)}
+    return {k: v for k, v in out.items() if k == "first" or n > 1}
+
+
+def edge_placements(edge_index, c, unroll=8):
+    """The placements of a poison in an edge-valued [E, c] input: edge 0, and the last input edge of a destination
+    whose in-degree is not a multiple of the kernels' unroll (its tail iteration is partly predicated off)."""
+    dst = np.asarray(edge_index[1])
+    out = {"edge0": (0, 0)}
+    deg = np.bincount(dst)
+    odd = [d for d in np.nonzero(deg % unroll)[0] if deg[d] >= 2]
+    if odd:
+        d = odd[len(odd) // 2]
+        out["segtail"] = (int(np.nonzero(dst == d)[0][-1]), c - 1)
+    return out
+
+
+def linear_spline_basis(a, kernel_size, is_open):
+    """The degree-1 B-spline basis of SplineConv in float32, as the kernel forms it: for
+    pseudo-coordinates ``a`` [E, D] in [0, 1] -> (b float32 [E, 2^D], wi int64 [E, 2^D]).  Per dimension ``v = a_d *
+    (kernel_size_d - open_d)``, ``f = v - floor(v)``; slot ``s`` takes digit ``k_d = (s >> d) & 1`` (dimension 0 runs
+    fastest), the factor ``1 - f - k_d + 2 f k_d`` and the index digit ``(floor(v) + k_d) mod kernel_size_d``."""
+    a = np.asarray(a, np.float32).reshape(len(a), -1)
+    dim = a.shape[1]
+    slots = np.arange(2 ** dim)
+    b = np.ones((a.shape[0], len(slots)), np.float32)
+    wi = np.zeros(b.shape, np.int64)
+    off = 1
+    for d in range(dim):
+        v = a[:, d] * np.float32(kernel_size[d] - int(bool(is_open[d])))
+        fl = np.floor(v)
+        f = (v - fl).astype(np.float32)[:, None]
+        k = ((slots >> d) & 1)[None]
+        wi += ((fl.astype(np.int64)[:, None] + k) % kernel_size[d]) * off
+        off *= kernel_size[d]
+        kf = k.astype(np.float32)
+        b = (b * (1 - f - kf + 2 * f * kf)).astype(np.float32)
+    return b, wi

@@ -77,6 +77,9 @@ _SIGNATURES = {
     "dc_generic_dense_launches": (c_int64, [c_int]),
     "dc_kernel_trace": (None, [c_int]),
     "dc_kernel_trace_dump": (c_int64, [c_char_p, c_int64]),
+    "dc_launch_sites_dump": (c_int64, [c_char_p, c_int64]),
+    "dc_launch_coverage": (None, [c_int]),
+    "dc_launch_reached_dump": (c_int64, [c_char_p, c_int64]),
     "dc_hash_i64": (c_int, [_vp, c_int64, _vp, _vp]),
     "dc_morton_codes": (c_int, [_vp, c_int64, c_int64, POINTER(c_float), POINTER(c_float), _vp, _vp]),
     "dc_morton_order_workspace_bytes": (c_int64, [c_int64]),
@@ -275,7 +278,69 @@ def lib():
                     f"{SO_PATH} does not export {name}; rebuild the library") from e
             fn.restype, fn.argtypes = res, args
         _lib = handle
+        if os.environ.get(COVERAGE_ENV):
+            _start_coverage(os.environ[COVERAGE_ENV])
     return _lib
+
+
+# Launch-site coverage of a whole run ("Launch sites"): with DC_LAUNCH_COVERAGE_FILE set when the
+# library loads, every process (children that inherit the variable included) appends the sites it reached, one
+# "site \t test id at the first reach" line each, to that file when it exits.
+COVERAGE_ENV = "DC_LAUNCH_COVERAGE_FILE"
+
+
+def _start_coverage(path: str) -> None:
+    import atexit
+    _lib.dc_launch_coverage(1)
+
+    def _append():
+        lines = [f"{site}\t{test}\n" for site, test in launch_reached().items()]
+        if lines:
+            with open(path, "a") as f:      # one write per process: appends of concurrent children do not interleave
+                f.write("".join(lines))
+    atexit.register(_append)
+
+
+def _dump(fn) -> list:
+    n = int(fn(None, 0))
+    buf = ctypes.create_string_buffer(n + 1)
+    fn(buf, n + 1)
+    return buf.value.decode().splitlines()
+
+
+def launch_site_files() -> dict:
+    """``{site: source file}`` for every launch site the library was built with (no GPU needed).  A site is
+    ``kernel text @ enclosing host function``; a templated launcher gives one site per instantiation."""
+    out = {}
+    for line in _dump(lib().dc_launch_sites_dump):
+        src, _, site = line.partition("\t")
+        out[site] = src
+    return out
+
+
+def launch_sites() -> list:
+    """Every launch site of the library (see ``launch_site_files``)."""
+    return list(launch_site_files())
+
+
+def launch_coverage(on: bool) -> None:
+    """Start / stop adding launched sites to the cumulative reached set (``dc_launch_coverage``)."""
+    lib().dc_launch_coverage(1 if on else 0)
+
+
+def launch_reached() -> dict:
+    """``{site: PYTEST_CURRENT_TEST at its first launch}`` for the sites reached while coverage was on."""
+    return {site: test for site, test, _ in _reached_rows()}
+
+
+def _reached_rows():
+    return [line.split("\t") for line in _dump(lib().dc_launch_reached_dump)]
+
+
+def launch_site_counts() -> dict:
+    """``{site: launches while coverage was on}`` for the reached sites; the difference around a call names exactly
+    the sites that call launched, whatever ran earlier in the process."""
+    return {site: int(n) for site, _, n in _reached_rows()}
 
 
 def check(rc: int, what: str) -> None:

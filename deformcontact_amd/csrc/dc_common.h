@@ -14,11 +14,28 @@ constexpr int kXcds = 8;       // MI355X: 8 XCDs, each with a private 4 MiB L2
 
 void set_error(const char *fmt, ...);
 
-// launch log (dc_kernel_trace / dc_kernel_trace_dump, dc_core.hip): off unless a test or tool switches it on
+// launch log (dc_kernel_trace / dc_kernel_trace_dump, dc_core.hip): off unless a test or tool switches it on.
+// g_trace_on is a bit set: kTraceLog (the launch log counts) | kTraceCoverage (dc_launch_coverage: the cumulative set
+// of launch sites reached), so that a launch pays ONE predictable branch when both are off
+constexpr int kTraceLog = 1, kTraceCoverage = 2;
 extern int g_trace_on;
 void trace_kernel_slow(const char *name);
 inline void trace_kernel(const char *name) {
     if (__builtin_expect(g_trace_on, 0)) trace_kernel_slow(name);
+}
+
+// One record per launch site, emitted into the link section "dc_sites" by DC_LAUNCH / DC_LAUNCH_SITE: the library
+// lists its own launches (dc_launch_sites_dump walks __start_dc_sites .. __stop_dc_sites; host code only, no GPU
+// needed).  A templated host launcher yields one record per instantiation, told apart by `where`
+// (__PRETTY_FUNCTION__ names the template arguments).
+struct Site {
+    const char *kernel;   // the kernel expression as written at the site
+    const char *where;    // __PRETTY_FUNCTION__ of the enclosing host function
+    const char *file;     // __FILE__
+};
+void trace_site_slow(const Site *site, const char *name);
+inline void trace_site(const Site *site, const char *name) {
+    if (__builtin_expect(g_trace_on, 0)) trace_site_slow(site, name);
 }
 
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
@@ -93,12 +110,25 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
 
 }  // namespace dc
 
-// every kernel launch of the library: the kernel expression as written (template arguments included) goes to the
-// launch log when it is on
+// the static record of one launch site (dc::Site), placed in the link section the library walks
+#define DC_SITE_RECORD(text) \
+    static const dc::Site dc_site_ __attribute__((section("dc_sites"), used)) = {text, __PRETTY_FUNCTION__, __FILE__}
+
+// every kernel launch of the library: the site is on record (DC_SITE_RECORD), and the kernel expression as written
+// (template arguments included) goes to the launch log / the site to the reached set when they are on
 #define DC_LAUNCH(kernel, ...)                     \
     do {                                           \
-        dc::trace_kernel(#kernel);                 \
+        DC_SITE_RECORD(#kernel);                   \
+        dc::trace_site(&dc_site_, #kernel);        \
         hipLaunchKernelGGL(kernel, __VA_ARGS__);   \
+    } while (0)
+
+// a launch written out by hand (hipLaunchKernelGGL with a name of its own in the launch log): registers the site
+// under `name`, which must have static storage and a constant address
+#define DC_LAUNCH_SITE(name)                 \
+    do {                                     \
+        DC_SITE_RECORD(name);                \
+        dc::trace_site(&dc_site_, name);     \
     } while (0)
 
 // the global source and the LDS destination of the LDS-DMA builtins (__builtin_amdgcn_global_load_lds,

@@ -499,6 +499,32 @@ k_hop_chain_gcn(ChainParams p) {
 #endif
 }
 
+// the launch-log name of one instantiation, e.g. "k_hop_chain<true, 3, 8>", as a constant: the launch-site record
+// (DC_LAUNCH_SITE) points at it
+struct ChainName {
+    char s[48];
+};
+static constexpr ChainName chain_name(const char *base, int w, int steps, int lpr) {
+    ChainName n = {};
+    int k = 0;
+    auto put = [&](const char *t) {
+        while (*t) n.s[k++] = *t++;
+    };
+    auto num = [&](int v) {
+        if (v >= 10) n.s[k++] = (char)('0' + v / 10);
+        n.s[k++] = (char)('0' + v % 10);
+    };
+    put(base);
+    if (w >= 0) put(w ? "true, " : "false, ");
+    num(steps);
+    if (lpr > 0) {
+        put(", ");
+        num(lpr);
+    }
+    put(">");
+    return n;
+}
+
 template <int STEPS>
 static bool launch_chain_gcn_steps(unsigned grid, hipStream_t stream, const ChainParams &p) {
     constexpr int R = 128 * STEPS;
@@ -516,8 +542,8 @@ static bool launch_chain_gcn_steps(unsigned grid, hipStream_t stream, const Chai
             return false;
         attr_set = true;
     }
-    static const std::string name = "k_hop_chain_gcn<" + std::to_string(STEPS) + ">";
-    trace_kernel(name.c_str());
+    static constexpr ChainName name = chain_name("k_hop_chain_gcn<", -1, STEPS, 0);
+    DC_LAUNCH_SITE(name.s);
     hipLaunchKernelGGL((k_hop_chain_gcn<STEPS>), dim3(grid), dim3(1024), lds_req, stream, p);
     return true;
 }
@@ -548,20 +574,28 @@ static bool launch_chain_steps(unsigned grid, hipStream_t stream, const ChainPar
             return false;
         attr_set = true;
     }
-    static const std::string name = std::string("k_hop_chain<") + (W ? "true, " : "false, ") + std::to_string(STEPS) + ", " +
-                                    std::to_string(LPR) + ">";
-    trace_kernel(name.c_str());
+    static constexpr ChainName name = chain_name("k_hop_chain<", W ? 1 : 0, STEPS, LPR);
+    DC_LAUNCH_SITE(name.s);
     hipLaunchKernelGGL((k_hop_chain<W, STEPS, LPR>), dim3(grid), dim3(1024), kChainLdsRequest, stream, p);
     return true;
 }
 
 template <bool W, int LPR>
 static bool launch_chain(int steps, unsigned grid, hipStream_t stream, const ChainParams &p) {
+    // the narrower slices (LPR 4 / 2) are chosen only for a largest graph beyond 1,024 / 2,048 nodes, at 256 / 512 rows
+    // per step: always 5..8 steps.  Fewer steps exist with 32-column slices only (no instantiation nothing can launch);
+    // a smaller count with narrow slices would take the 8-step form below, which is correct for it as well: STEPS is
+    // the kernel's row CAPACITY (every launch also walks graphs smaller than its largest)
+    if constexpr (LPR == 8) {
+        switch (steps) {
+        case 1: return launch_chain_steps<W, 1, LPR>(grid, stream, p);
+        case 2: return launch_chain_steps<W, 2, LPR>(grid, stream, p);
+        case 3: return launch_chain_steps<W, 3, LPR>(grid, stream, p);
+        case 4: return launch_chain_steps<W, 4, LPR>(grid, stream, p);
+        default: break;
+        }
+    }
     switch (steps) {
-    case 1: return launch_chain_steps<W, 1, LPR>(grid, stream, p);
-    case 2: return launch_chain_steps<W, 2, LPR>(grid, stream, p);
-    case 3: return launch_chain_steps<W, 3, LPR>(grid, stream, p);
-    case 4: return launch_chain_steps<W, 4, LPR>(grid, stream, p);
     case 5: return launch_chain_steps<W, 5, LPR>(grid, stream, p);
     case 6: return launch_chain_steps<W, 6, LPR>(grid, stream, p);
     case 7: return launch_chain_steps<W, 7, LPR>(grid, stream, p);

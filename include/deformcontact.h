@@ -610,6 +610,23 @@ int64_t dc_generic_dense_launches(int reset);
 void dc_kernel_trace(int on);
 int64_t dc_kernel_trace_dump(char *buf, int64_t cap);
 
+/* Launch sites: the library lists its own kernel launches.  Every launch in the sources leaves one static record in
+ * the library's data (host code only: the list needs no GPU); a templated host launcher leaves one per instantiation.
+ * A site's identity is "kernel text @ enclosing host function", the kernel text as in the launch log, the function as
+ * the compiler prints it with its template arguments, e.g.
+ *     k_hop_chain<true, 3, 8> @ bool dc::launch_chain_steps(...) [W = true, STEPS = 3, LPR = 8]
+ * (a second launch of the same kernel text in one function gets " #2").
+ * dc_launch_sites_dump writes one "source file\tidentity\n" line per site.  dc_launch_coverage(1) starts, (0) stops
+ * adding every site that launches to a cumulative reached set, which is never cleared and is independent of
+ * dc_kernel_trace; dc_launch_reached_dump writes one "identity\ttest\tlaunches\n" line per reached site, `test` being
+ * the environment's PYTEST_CURRENT_TEST at the site's first launch (empty when unset) and `launches` the site's launches
+ * while coverage was on (its difference around a call names exactly the sites that call launched).  Both dumps fill buf like
+ * dc_kernel_trace_dump and return the size the whole text needs.  Off by default, at no cost beyond the launch
+ * log's one predictable branch. */
+int64_t dc_launch_sites_dump(char *buf, int64_t cap);
+void dc_launch_coverage(int on);
+int64_t dc_launch_reached_dump(char *buf, int64_t cap);
+
 /* rowmax[i] = max |x[i, 0:F]| for a row-major [N, F] view with leading dimension ld. */
 int dc_rowabsmax_f32(const float *x, int64_t ld, int64_t N, int64_t F, float *rowmax,
                      dc_stream_t stream);

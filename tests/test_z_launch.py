@@ -91,7 +91,9 @@ def test_direct_multi_gpu_launch_stops_stalled_ranks_at_its_deadline(tmp_path):
     """Every rank stalls (DC_TEST_STALL_RANK=all): the launcher stops them at DC_LAUNCH_TIMEOUT and returns non-zero."""
     if torch.cuda.device_count() > 0:
         pytest.skip("a GPU is visible: GPU child processes are only started by tests/launch_scenarios.py")
-    env = dict(os.environ, DC_RANK_LOG_DIR=str(tmp_path), DC_TEST_STALL_RANK="all", DC_LAUNCH_TIMEOUT="4")
+    # the deadline has to leave a rank the time to import torch and write its first marker: a rank stopped before that
+    # has no phase to show
+    env = dict(os.environ, DC_RANK_LOG_DIR=str(tmp_path), DC_TEST_STALL_RANK="all", DC_LAUNCH_TIMEOUT="10")
     r, wall = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0"], env)
     assert r.returncode != 0 and wall < 60
     assert b"launch deadline" in r.stderr

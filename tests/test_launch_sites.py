@@ -209,6 +209,7 @@ def _dense_fwd(d, relu, products, bias=True):
     else:
         call = lambda: _lib.check(L.dc_tag_linear_fwd(*args, d.st), "fwd")
     counts = _trace(call)
+    d.outputs = [out]                                      # the device tensors (tests/test_guard_bands.py)
     ref = sum(d.x64[s] @ d.w64[s].t() for s in range(d.nseg))
     if bias:
         ref = ref + d.bias.double().cpu()
@@ -241,6 +242,7 @@ def _dense_dx(d, mask, products):
     else:
         call = lambda: _lib.check(L.dc_tag_linear_bwd_dx(*head, d.n, d.fi, d.fo, d.st), "dx")
     counts = _trace(call)
+    d.outputs = [gslab]
     gm = d.gm64(mask)
     return counts, [(f"gx[{s}]", gxs[s].cpu().numpy(), (gm @ d.w64[s]).numpy(), TOL[products])
                     for s in range(d.nseg)]
@@ -263,6 +265,7 @@ def _dense_dw(d, mask, products, accumulate=0, bps=1, gbias=True):
             d.n, d.fi, d.fo)
     counts = _trace(lambda: _lib.check(L.dc_tag_linear_bwd_dw_split(*args, products, d.st) if products
                                        else L.dc_tag_linear_bwd_dw(*args, d.st), "dw"))
+    d.outputs = gws + ([gb] if gbias else [])
     gm = d.gm64(mask)
     base = 0.25 if accumulate else 0.0
     cmp = []
@@ -436,17 +439,15 @@ def test_hop_chain_site_vs_float64(kernel, big, weighted, gcn):
         assert e < 1e-5, (j, e)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("f,kernel,form", [(37, "k_spmm_bf16x1<L, 8, OUT_F32>", "L = 64, X8 = false"),
-                                           (96, "k_spmm_bf16x8<L, 8, OUT_F32>", "L = 16, X8 = true")])
-def test_bf16_hop_site_vs_float64(f, kernel, form):
-    """dc_spmm_bf16 at the widths that pick 64 lanes per row of the any-alignment kernel (32 < F, F % 8 != 0) and 16
-    lanes per row of the 16-byte kernel (64 < F <= 128), with an addend.  The fp32 output within 1e-5 per row of
-    float64; the bf16 output equal bit for bit to that fp32 output rounded once to bf16 (the addend holds bf16 values in
-    both calls, so both accumulate the same fp32 sum: all the bf16 form adds is the one rounding on store)."""
+BF16_HOP_ROWS = [(37, "k_spmm_bf16x1<L, 8, OUT_F32>", "L = 64, X8 = false"),
+                 (96, "k_spmm_bf16x8<L, 8, OUT_F32>", "L = 16, X8 = true")]
+
+
+def _bf16_hop_run(f, kernel, form):
+    """-> (graph, x, addend, {out_f32: y}): both output types of one bf16 hop, the site of each asserted"""
     from deformcontact_amd import ops
     from deformcontact_amd.graph import GraphIndex
-    from tests.helpers import random_multigraph, row_rel_err
+    from tests.helpers import random_multigraph
     n, e = 333, 2500
     g = GraphIndex(torch.from_numpy(random_multigraph(n, e, f)).to(DEV), n)
     xb = _rand((n, f), 7, 2.0).to(DEV).bfloat16()
@@ -457,6 +458,18 @@ def test_bf16_hop_site_vs_float64(f, kernel, form):
         counts = _trace(lambda: ys.update({out_f32: ops.hop_bf16(g.fwd, xb, addend=add.to(dt), out_dtype=dt)}))
         assert len(counts) == 1, dict(counts)
         _assert_launched(counts, f"{kernel} | [{form}, OUT_F32 = {'true' if out_f32 else 'false'}]", 1)
+    return g, xb, add, ys
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("f,kernel,form", BF16_HOP_ROWS)
+def test_bf16_hop_site_vs_float64(f, kernel, form):
+    """dc_spmm_bf16 at the widths that pick 64 lanes per row of the any-alignment kernel (32 < F, F % 8 != 0) and 16
+    lanes per row of the 16-byte kernel (64 < F <= 128), with an addend.  The fp32 output within 1e-5 per row of
+    float64; the bf16 output equal bit for bit to that fp32 output rounded once to bf16 (the addend holds bf16 values in
+    both calls, so both accumulate the same fp32 sum: all the bf16 form adds is the one rounding on store)."""
+    from tests.helpers import row_rel_err
+    g, xb, add, ys = _bf16_hop_run(f, kernel, form)
     ref = add.double().cpu().numpy() + _csr_apply64(g.fwd, xb.double().cpu().numpy())
     err = row_rel_err(ys[True].double().cpu().numpy(), ref)
     print(f"rel_err per row {err:.3e}")
@@ -464,17 +477,16 @@ def test_bf16_hop_site_vs_float64(f, kernel, form):
     assert ys[False].dtype == torch.bfloat16 and torch.equal(ys[False], ys[True].bfloat16())
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("fi,kernel_l", [(16, 16), (9, 16), (8, 8), (3, 8)])
-def test_pack_with_weight_image_at_narrow_inputs(fi, kernel_l):
-    """dc_spmm_f32_pack_wprep with 16 / 8 lanes per row (F <= 16 / F <= 8; the shipped first layers have F = 21 / 25):
-    the weight image equal bit for bit to the CPU restatement of the three bf16 planes, block 0 the input, block 1 the
-    first hop within 1e-5 per row of float64, the K padding zero."""
+PACK_WPREP_ROWS = [(16, 16), (9, 16), (8, 8), (3, 8)]
+
+
+def _pack_wprep_run(fi, kernel_l):
+    """-> (adjacency, weights, x, slab, weight image) of one dc_spmm_f32_pack_wprep launch, its site asserted"""
     from deformcontact_amd import _lib
     from deformcontact_amd.graph import GraphIndex, current_stream_ptr
     from deformcontact_amd.ops import _ptr_array
-    from tests.helpers import random_multigraph, row_rel_err
-    from tests.test_narrow_prepared import _check_image, _image_buffer, _weights
+    from tests.helpers import random_multigraph
+    from tests.test_narrow_prepared import _image_buffer, _weights
     L = _lib.lib()
     n, e, nseg, wpad = 1003, 7001, 4, 96
     st = current_stream_ptr(torch.device(DEV))
@@ -489,6 +501,19 @@ def test_pack_with_weight_image_at_narrow_inputs(fi, kernel_l):
         adj.ptr.data_ptr(), adj.other.data_ptr(), adj.w.data_ptr(), x.data_ptr(), x.stride(0), slab.data_ptr(),
         slab.stride(0), n, fi, width, wpad, _ptr_array(ws), nseg, buf.data_ptr(), st), "pack_wprep"))
     _assert_launched(counts, f"k_spmm_sub_wimg<L, 8> | [L = {kernel_l}]", 1)
+    return adj, ws, x, slab, buf
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fi,kernel_l", PACK_WPREP_ROWS)
+def test_pack_with_weight_image_at_narrow_inputs(fi, kernel_l):
+    """dc_spmm_f32_pack_wprep with 16 / 8 lanes per row (F <= 16 / F <= 8; the shipped first layers have F = 21 / 25):
+    the weight image equal bit for bit to the CPU restatement of the three bf16 planes, block 0 the input, block 1 the
+    first hop within 1e-5 per row of float64, the K padding zero."""
+    from tests.helpers import row_rel_err
+    from tests.test_narrow_prepared import _check_image
+    nseg, wpad, width = 4, 96, 4 * fi
+    adj, ws, x, slab, buf = _pack_wprep_run(fi, kernel_l)
     _check_image(buf, ws, fi, nseg, wpad)
     got = slab.cpu().numpy()
     assert np.array_equal(got[:, :fi], x.cpu().numpy())
@@ -498,11 +523,8 @@ def test_pack_with_weight_image_at_narrow_inputs(fi, kernel_l):
     assert err < 1e-5, err
 
 
-@pytest.mark.gpu
-def test_morton_codes_entry():
-    """dc_morton_codes (`k_morton`): 10 bits per axis of (pos - lo) * inv_extent * 1024, clamped to [0, 1023] and
-    interleaved x, y, z from bit 0.  Equal to the float32 restatement of the same three operations; a float64 evaluation
-    may put a point that sits on a cell boundary into the neighbouring cell, never further."""
+def _morton_codes_run():
+    """-> (positions on the host, lo, 1 / extent, codes on the device) of one dc_morton_codes launch, its site asserted"""
     import ctypes
     from deformcontact_amd import _lib
     from deformcontact_amd.graph import current_stream_ptr
@@ -516,6 +538,16 @@ def test_morton_codes_entry():
         pos.data_ptr(), ld, n, F3(*lo), F3(*inv), codes.data_ptr(), current_stream_ptr(torch.device(DEV))), "morton"))
     assert len(counts) == 1, dict(counts)
     _assert_launched(counts, "k_morton", 1)
+    return base, lo, inv, codes
+
+
+@pytest.mark.gpu
+def test_morton_codes_entry():
+    """dc_morton_codes (`k_morton`): 10 bits per axis of (pos - lo) * inv_extent * 1024, clamped to [0, 1023] and
+    interleaved x, y, z from bit 0.  Equal to the float32 restatement of the same three operations; a float64 evaluation
+    may put a point that sits on a cell boundary into the neighbouring cell, never further."""
+    base, lo, inv, codes = _morton_codes_run()
+    n = base.shape[0]
     p = base.numpy()[:, :3]
 
     def cells(dtype):

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .graph import _require_cuda, current_stream_ptr
-from .ops import _i64_array, _ptr_array
+from ._host import _i64_array, _ptr_array
 
 import os
 

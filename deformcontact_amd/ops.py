@@ -5,44 +5,22 @@ reference (``models/model.py:71,77``), with every gather /
 scatter step executed by ``libdeformcontact_hip.so`` on the current HIP stream.
 PyTorch is used for device memory, autograd bookkeeping and (for now) the plain
 dense GEMMs.
+
+This module holds the benchmarked path (the hops, the hop chain and cache, TAGConv in its fp32, grouped and bf16 forms,
+the contact loss), EVERY run-time switch of the package, and - re-exported at its end - the public functions of the
+other layers, whose code is in ``deformcontact_amd/layers/``.
 """
 from __future__ import annotations
 
-import ctypes
-import math
 import os
 from typing import List, Optional
 
 import torch
 
 from . import _lib
+from ._host import _grad_layout, _i64_array, _ptr, _ptr_array, _rowmajor, _vp_array
 from .deferred import resolve
-from .graph import GraphIndex, SortedAdjacency, _require_cuda, capture_id, current_stream_ptr, graph_index
-
-
-def _rowmajor(t: torch.Tensor, what: str, dtypes=(torch.float32,)) -> int:
-    """Return the leading dimension of a 2-D row-major (possibly column-sliced) view of one of ``dtypes``."""
-    if t.dim() != 2 or t.dtype not in dtypes:
-        raise ValueError(f"{what}: expected a 2-D tensor of {dtypes}, got {tuple(t.shape)} {t.dtype}")
-    if t.size(1) > 1 and t.stride(1) != 1:
-        raise ValueError(f"{what}: innermost dimension must be contiguous")
-    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
-
-
-def _vp_array(ptrs):
-    return (ctypes.c_void_p * len(ptrs))(*ptrs)
-
-
-def _ptr_array(tensors):
-    return _vp_array([t.data_ptr() for t in tensors])
-
-
-def _i64_array(vals):
-    return (ctypes.c_int64 * len(vals))(*vals)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
+from .graph import GraphIndex, SortedAdjacency, _require_cuda, capture_id, current_stream_ptr
 
 
 def _spmm(adj: SortedAdjacency, w: Optional[torch.Tensor], x: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -157,14 +135,6 @@ class _HopFn(torch.autograd.Function):
 def propagate(g: GraphIndex, x: torch.Tensor, weighted: bool = True) -> torch.Tensor:
     """Autograd-aware hop (PyG ``propagate(edge_index, x=x, edge_weight=w)``)."""
     return _HopFn.apply(g, resolve(x), weighted)
-
-
-def _grad_layout(g: torch.Tensor, row_align: int) -> torch.Tensor:
-    """The incoming gradient ``g`` in a layout the backward kernels of the calling site take, copied only if it is not
-    in one already.  ``row_align`` = 0: dense rows (plain contiguous); 1: unit inner stride, any row stride (column
-    slices pass as they are); 4: unit inner stride, and row stride and base address multiples of 4 floats (16 bytes)."""
-    ok = row_align == 1 or (row_align == 4 and g.stride(0) % 4 == 0 and g.data_ptr() % 16 == 0)
-    return g if (ok and g.stride(1) == 1) else g.contiguous()
 
 
 MAX_SEG = 4   # DC_MAX_SEG in include/deformcontact.h
@@ -1213,698 +1183,6 @@ def tag_conv_bf16(g: GraphIndex, x: torch.Tensor, weights, bias, relu: bool = Fa
 
 
 # --------------------------------------------------------------------------- #
-# GATConv (heads = 1): edge softmax + weighted aggregation
-# --------------------------------------------------------------------------- #
-def _gat_edge_softmax(g: GraphIndex, a_src: torch.Tensor, a_dst: torch.Tensor, slope: float, n: int) -> torch.Tensor:
-    """``alpha[p] = softmax over the edges into i of leaky_relu(a_src[j] + a_dst[i])``, in ``g.fwd`` order."""
-    alpha = torch.zeros(max(g.capacity, 1), dtype=torch.float32, device=a_src.device)
-    _lib.check(_lib.lib().dc_gat_edge_softmax_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
-                                                  a_dst.data_ptr(), slope, alpha.data_ptr(), n,
-                                                  current_stream_ptr(a_src.device)), "dc_gat_edge_softmax_fwd")
-    return alpha
-
-
-def _gat_edge_backward(g: GraphIndex, gm, h, a_src, a_dst, alpha, slope: float):
-    """Backward of ``out = sum_j alpha_ij h_j`` with ``alpha`` = ``_gat_edge_softmax``, from the gradient ``gm`` of
-    ``out``: -> (gh, g_a_src, g_a_dst)."""
-    L = _lib.lib()
-    n, f = h.shape
-    dev = h.device
-    st = current_stream_ptr(dev)
-    cap = max(g.capacity, 1)
-    b2f = g.bwd_to_fwd()
-    cnt = g.fwd.ptr[-1:]
-    # d out / d h : transposed aggregation with alpha re-ordered by source
-    alpha_b = torch.zeros(cap, dtype=torch.float32, device=dev)
-    _lib.check(L.dc_gather_f32(alpha.data_ptr(), b2f.data_ptr(), alpha_b.data_ptr(), cnt.data_ptr(), g.capacity, st),
-               "dc_gather_f32")
-    gh = _spmm(g.bwd, alpha_b, gm)
-    # d out / d alpha, through the softmax, summed per source
-    galpha = torch.zeros(cap, dtype=torch.float32, device=dev)
-    _lib.check(L.dc_sddmm_f32(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), gm.data_ptr(), f, h.data_ptr(), f,
-                              galpha.data_ptr(), n, f, st), "dc_sddmm_f32")
-    ge = torch.zeros(cap, dtype=torch.float32, device=dev)
-    g_a_dst = torch.empty(n, dtype=torch.float32, device=dev)
-    _lib.check(L.dc_gat_edge_softmax_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
-                                         a_dst.data_ptr(), slope, alpha.data_ptr(), galpha.data_ptr(),
-                                         ge.data_ptr(), g_a_dst.data_ptr(), n, st), "dc_gat_edge_softmax_bwd")
-    g_a_src = torch.empty(n, dtype=torch.float32, device=dev)
-    _lib.check(L.dc_segment_sum_f32(g.bwd.ptr.data_ptr(), b2f.data_ptr(), ge.data_ptr(), g_a_src.data_ptr(), n, st),
-               "dc_segment_sum_f32")
-    return gh, g_a_src, g_a_dst
-
-
-class _GatAggregateFn(torch.autograd.Function):
-    """The unfused GATConv aggregation (edge softmax + weighted sum); ``_GatConvFn`` is the whole layer."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, a_src, a_dst, slope: float):
-        h, a_src, a_dst = h.contiguous(), a_src.contiguous(), a_dst.contiguous()
-        alpha = _gat_edge_softmax(g, a_src, a_dst, slope, h.size(0))
-        out = _spmm(g.fwd, alpha, h)
-        ctx.g, ctx.slope = g, slope
-        ctx.save_for_backward(h, a_src, a_dst, alpha)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        h, a_src, a_dst, alpha = ctx.saved_tensors
-        gh, g_a_src, g_a_dst = _gat_edge_backward(ctx.g, _grad_layout(gout, 0), h, a_src, a_dst, alpha, ctx.slope)
-        return None, gh, g_a_src, g_a_dst, None
-
-
-def gat_aggregate(g: GraphIndex, h, a_src, a_dst, slope: float) -> torch.Tensor:
-    return _GatAggregateFn.apply(g, h, a_src, a_dst, float(slope))
-
-
-# --------------------------------------------------------------------------- #
-# GCNConv / GATConv: aggregation + bias + ReLU as one node, row-wise passes fused (dc_gnn_epi.hip)
-# --------------------------------------------------------------------------- #
-FUSED_GNN_EPILOGUE = True          # (False: the unfused layer composition - tests compare the two)
-
-
-def fused_gnn_ok(h: torch.Tensor) -> bool:
-    """Widths / layouts the fused GCN / GAT layer kernels take (F % 4 == 0, F / 4 divides 256, aligned rows)."""
-    f = h.size(1)
-    return (FUSED_GNN_EPILOGUE and h.is_cuda and h.dtype == torch.float32 and f % 4 == 0 and 4 <= f <= 1024
-            and 256 % (f // 4) == 0)
-
-
-def _agg_bias_act(adj: SortedAdjacency, w: torch.Tensor, h: torch.Tensor, bias, relu: bool) -> torch.Tensor:
-    n, f = h.shape
-    y = torch.empty((n, f), dtype=torch.float32, device=h.device)
-    _lib.check(_lib.lib().dc_spmm_f32_bias_act(adj.ptr.data_ptr(), adj.other.data_ptr(), w.data_ptr(), h.data_ptr(),
-                                               _rowmajor(h, "h"), _ptr(bias), int(relu), y.data_ptr(), f, n, f,
-                                               current_stream_ptr(h.device)), "dc_spmm_f32_bias_act")
-    return y
-
-
-def _mask_and_bias_grad(gy: torch.Tensor, y: Optional[torch.Tensor], bias_param, need_bias: bool):
-    """gm = gy * (y > 0) (y None: gm is gy) and the bias gradient sum_i gm[i, :] in one pass.  The bias gradient
-    goes straight into the bucket's view in direct mode (-> None), else it is returned."""
-    n, f = gy.shape
-    dev = gy.device
-    if y is None and not need_bias:
-        return gy, None
-    L = _lib.lib()
-    gm = torch.empty((n, f), dtype=torch.float32, device=dev) if y is not None else None
-    sink = _direct_sink([bias_param], [need_bias and bias_param is not None])
-    direct = sink is not None
-    if need_bias:
-        gb = bias_param.grad if direct else torch.empty(f, dtype=torch.float32, device=dev)
-    else:
-        gb = torch.empty(f, dtype=torch.float32, device=dev)         # (the kernel always forms it: one pass either way)
-    nb = L.dc_colsum_workspace_bytes(n, f, 1)
-    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
-    _lib.check(L.dc_mask_colsum_f32(gy.data_ptr(), gy.stride(0), _ptr(y), y.stride(0) if y is not None else 0,
-                                    _ptr(gm), gm.stride(0) if gm is not None else 0, n, f, ws.data_ptr(), ws.numel(),
-                                    gb.data_ptr(), int(direct), current_stream_ptr(dev)), "dc_mask_colsum_f32")
-    if direct:
-        sink.note_direct_write(torch.cuda.current_stream(dev))
-    return (gm if gm is not None else gy), (None if (direct or not need_bias) else gb)
-
-
-class _ParamGrads:
-    """Where a backward kernel writes the gradients of ``params``: ``bufs`` are flat views of their ``.grad`` when the
-    kernel may accumulate there (``_direct_sink``; ``direct``), else fresh buffers.  ``done()`` behind the launch
-    reports the direct write, or shapes the buffers like the parameters: what ``backward`` returns for them."""
-
-    def __init__(self, params, needed, dev):
-        self.params, self.dev = params, dev
-        self.bucket = _direct_sink(params, needed)
-        self.direct = self.bucket is not None
-        self.bufs = [p.grad.view(-1) if self.direct else torch.empty(p.numel(), dtype=torch.float32, device=dev)
-                     for p in params]
-
-    def done(self):
-        if self.direct:
-            self.bucket.note_direct_write(torch.cuda.current_stream(self.dev))
-            return [None] * len(self.params)
-        return [b.view_as(p) for b, p in zip(self.bufs, self.params)]
-
-
-class _GcnAggFn(torch.autograd.Function):
-    """``act(A_hat h + bias)`` of a GCNConv layer (PyG gcn_conv.py: ``propagate`` + ``out + bias``, then the encoder's
-    ReLU, models/model.py:71,77) as ONE aggregation launch; backward: mask + bias gradient in one pass, then the
-    transposed aggregation."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, bias, relu: bool):
-        h = h.contiguous()
-        y = _agg_bias_act(g.fwd, g.fwd.w, h, bias, relu)
-        ctx.g, ctx.relu, ctx.bias_param = g, relu, bias
-        ctx.save_for_backward(y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (y,) = ctx.saved_tensors
-        gy = _grad_layout(gy, 0)
-        need_b = ctx.bias_param is not None and ctx.needs_input_grad[2]
-        gm, gb = _mask_and_bias_grad(gy, y, ctx.bias_param, need_b)
-        gh = hop(ctx.g.bwd, gm, weighted=True) if ctx.needs_input_grad[1] else None
-        return None, gh, gb, None
-
-
-def gcn_aggregate(g: GraphIndex, h: torch.Tensor, bias, relu: bool = False) -> torch.Tensor:
-    return _GcnAggFn.apply(g, resolve(h), bias, bool(relu))
-
-
-class _GatConvFn(torch.autograd.Function):
-    """Everything of a GATConv layer (heads = 1) behind its ``lin``: both attention dot products in one pass over h,
-    edge softmax, ``act(sum_j a_ij h_j + bias)`` as one aggregation launch; backward: mask + bias gradient in one
-    pass, transposed aggregation, SDDMM + softmax backward, and the dot products' backward (rank-one updates of dh
-    and the two attention-vector gradients) in one pass (PyG gat_conv.py, utils/_softmax.py)."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool):
-        L = _lib.lib()
-        h = h.contiguous()
-        n, f = h.shape
-        dev = h.device
-        st = current_stream_ptr(dev)
-        a_s, a_d = att_src.reshape(-1).contiguous(), att_dst.reshape(-1).contiguous()
-        a_src = torch.empty(n, dtype=torch.float32, device=dev)
-        a_dst = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.check(L.dc_gat_alpha_fwd(h.data_ptr(), f, a_s.data_ptr(), a_d.data_ptr(), a_src.data_ptr(),
-                                      a_dst.data_ptr(), n, f, st), "dc_gat_alpha_fwd")
-        alpha = _gat_edge_softmax(g, a_src, a_dst, slope, n)
-        y = _agg_bias_act(g.fwd, alpha, h, bias, relu)
-        ctx.g, ctx.slope, ctx.relu = g, slope, relu
-        ctx.params = (att_src, att_dst, bias)
-        ctx.save_for_backward(h, a_src, a_dst, alpha, a_s, a_d, y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        L = _lib.lib()
-        h, a_src, a_dst, alpha, a_s, a_d, y = ctx.saved_tensors
-        g, slope = ctx.g, ctx.slope
-        att_src, att_dst, bias = ctx.params
-        gy = _grad_layout(gy, 0)
-        n, f = h.shape
-        dev = h.device
-        st = current_stream_ptr(dev)
-        need_b = bias is not None and ctx.needs_input_grad[4]
-        gm, gb = _mask_and_bias_grad(gy, y, bias, need_b)
-        gh, g_a_src, g_a_dst = _gat_edge_backward(g, gm, h, a_src, a_dst, alpha, slope)
-        # the attention dot products' backward: gh += ga_src att_src + ga_dst att_dst, the two vector gradients
-        pg = _ParamGrads([att_src, att_dst], ctx.needs_input_grad[2:4], dev)
-        gs, gd = pg.bufs
-        nb = L.dc_colsum_workspace_bytes(n, f, 2)
-        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
-        _lib.check(L.dc_gat_alpha_bwd(h.data_ptr(), f, g_a_src.data_ptr(), g_a_dst.data_ptr(), a_s.data_ptr(),
-                                      a_d.data_ptr(), gh.data_ptr(), f, n, f, ws.data_ptr(), ws.numel(), gs.data_ptr(),
-                                      gd.data_ptr(), int(pg.direct), st), "dc_gat_alpha_bwd")
-        gs, gd = pg.done()
-        return None, gh, gs, gd, gb, None, None
-
-
-def gat_conv(g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool = False) -> torch.Tensor:
-    return _GatConvFn.apply(g, resolve(h), att_src, att_dst, bias, float(slope), bool(relu))
-
-
-# --------------------------------------------------------------------------- #
-# GATConv with several heads (dc_gat_heads.hip): h is [N, H*C], per-node vectors [N, H], per-edge vectors
-# [capacity, H] edge-major in g.fwd order.  One launcher per C entry.
-# --------------------------------------------------------------------------- #
-def _heads_alpha_fwd(h, a_s, a_d, nh: int, c: int):
-    """(a_src, a_dst) [N, H]: both attention dot products of every head in one pass over ``h``."""
-    n, dev = h.size(0), h.device
-    a_src = torch.empty((n, nh), dtype=torch.float32, device=dev)
-    a_dst = torch.empty((n, nh), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_gat_alpha_heads_fwd(h.data_ptr(), _rowmajor(h, "h"), a_s.data_ptr(), a_d.data_ptr(),
-                                                 a_src.data_ptr(), a_dst.data_ptr(), n, nh, c, current_stream_ptr(dev)),
-               "dc_gat_alpha_heads_fwd")
-    return a_src, a_dst
-
-
-def _heads_edge_vector(g: GraphIndex, nh: int, dev) -> torch.Tensor:
-    return torch.zeros((max(g.capacity, 1), nh), dtype=torch.float32, device=dev)
-
-
-def _heads_softmax_fwd(g: GraphIndex, a_src, a_dst, slope: float, n: int, nh: int) -> torch.Tensor:
-    alpha = _heads_edge_vector(g, nh, a_src.device)
-    _lib.check(_lib.lib().dc_gat_edge_softmax_heads_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
-                                                        a_dst.data_ptr(), slope, alpha.data_ptr(), n, nh,
-                                                        current_stream_ptr(a_src.device)), "dc_gat_edge_softmax_heads_fwd")
-    return alpha
-
-
-def _heads_agg(adj: SortedAdjacency, alpha, x, bias, relu: bool, mean: bool, nh: int, c: int) -> torch.Tensor:
-    """``act(sum_p alpha[p, head] x[other[p]] + bias)`` at width H*C, or its mean over heads at width C."""
-    n, dev = x.size(0), x.device
-    y = torch.empty((n, c if mean else nh * c), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_spmm_f32_heads_bias_act(adj.ptr.data_ptr(), adj.other.data_ptr(), alpha.data_ptr(),
-                                                     x.data_ptr(), _rowmajor(x, "x"), _ptr(bias), int(relu), int(mean),
-                                                     y.data_ptr(), y.size(1), n, nh, c, current_stream_ptr(dev)),
-               "dc_spmm_f32_heads_bias_act")
-    return y
-
-
-def _heads_sddmm(g: GraphIndex, gm, h, nh: int, c: int) -> torch.Tensor:
-    galpha = _heads_edge_vector(g, nh, h.device)
-    _lib.check(_lib.lib().dc_sddmm_f32_heads(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), gm.data_ptr(),
-                                             _rowmajor(gm, "gm"), h.data_ptr(), _rowmajor(h, "h"), galpha.data_ptr(),
-                                             h.size(0), nh, c, current_stream_ptr(h.device)), "dc_sddmm_f32_heads")
-    return galpha
-
-
-def _heads_softmax_bwd(g: GraphIndex, a_src, a_dst, slope: float, alpha, galpha, n: int, nh: int):
-    dev = alpha.device
-    ge = _heads_edge_vector(g, nh, dev)
-    g_a_dst = torch.empty((n, nh), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_gat_edge_softmax_heads_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
-                                                        a_dst.data_ptr(), slope, alpha.data_ptr(), galpha.data_ptr(),
-                                                        ge.data_ptr(), g_a_dst.data_ptr(), n, nh,
-                                                        current_stream_ptr(dev)), "dc_gat_edge_softmax_heads_bwd")
-    return ge, g_a_dst
-
-
-def _heads_segment_sum(ptr, index_map, v, n: int, w: int) -> torch.Tensor:
-    out = torch.empty((n, w), dtype=torch.float32, device=v.device)
-    _lib.check(_lib.lib().dc_segment_sum_f32_heads(ptr.data_ptr(), _ptr(index_map), v.data_ptr(), out.data_ptr(), n, w,
-                                                   current_stream_ptr(v.device)), "dc_segment_sum_f32_heads")
-    return out
-
-
-def _heads_gather(g: GraphIndex, v, idx, w: int) -> torch.Tensor:
-    """``out[p, :] = v[idx[p], :]`` for the edges the adjacency holds (counted on the device, ``g.fwd.ptr[-1]``)."""
-    out = _heads_edge_vector(g, w, v.device)
-    _lib.check(_lib.lib().dc_gather_f32_heads(v.data_ptr(), idx.data_ptr(), out.data_ptr(), g.fwd.ptr[-1:].data_ptr(),
-                                              g.capacity, w, current_stream_ptr(v.device)), "dc_gather_f32_heads")
-    return out
-
-
-def _heads_spread(gm, nh: int, c: int) -> torch.Tensor:
-    """The gradient of the mean over heads: ``out[i, k*C + c] = gm[i, c] / H``."""
-    n, dev = gm.size(0), gm.device
-    out = torch.empty((n, nh * c), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_spread_heads_f32(gm.data_ptr(), _rowmajor(gm, "gm"), out.data_ptr(), nh * c, n, nh, c,
-                                              current_stream_ptr(dev)), "dc_spread_heads_f32")
-    return out
-
-
-def _heads_out_grad(ctx, gy, y, bias):
-    """How the multi-head backward passes open: ``gy`` in a layout the kernels take, the ReLU mask and the bias
-    gradient in one pass (``bias`` is input 4 of every one of them), and - the heads averaged - the gradient spread to
-    the heads.  -> (gm [N, H*C], gb)."""
-    gy = _grad_layout(gy, 0)
-    gm, gb = _mask_and_bias_grad(gy, y, bias, bias is not None and ctx.needs_input_grad[4])
-    if ctx.mean:
-        gm = _heads_spread(gm, ctx.nh, ctx.c)
-    return gm, gb
-
-
-def _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh: int, c: int, gs, gd, accumulate: bool) -> None:
-    n, f, dev = h.size(0), nh * c, h.device
-    L = _lib.lib()
-    ws = torch.empty(max(L.dc_colsum_workspace_bytes(n, f, 2), 16), dtype=torch.uint8, device=dev)
-    _lib.check(L.dc_gat_alpha_heads_bwd(h.data_ptr(), f, g_a_src.data_ptr(), g_a_dst.data_ptr(), a_s.data_ptr(),
-                                        a_d.data_ptr(), gh.data_ptr(), f, n, nh, c, ws.data_ptr(), ws.numel(),
-                                        gs.data_ptr(), gd.data_ptr(), int(accumulate), current_stream_ptr(dev)),
-               "dc_gat_alpha_heads_bwd")
-
-
-def _gat_heads_edge_backward(g: GraphIndex, gm, h, a_src, a_dst, alpha, slope: float, nh: int, c: int, a_edge=None):
-    """``_gat_edge_backward`` for H heads, from the gradient ``gm`` [N, H*C] of the concatenated aggregation:
-    -> (gh [N, H*C], g_a_src [N, H], g_a_dst [N, H], ge [capacity, H]); ``a_edge``: the logits' per-edge addend."""
-    n = h.size(0)
-    b2f = g.bwd_to_fwd()
-    # d out / d h : transposed aggregation with alpha re-ordered by source, H floats per edge
-    gh = _heads_agg(g.bwd, _heads_gather(g, alpha, b2f, nh), gm, None, False, False, nh, c)
-    # d out / d alpha, through the softmax, summed per source
-    galpha = _heads_sddmm(g, gm, h, nh, c)
-    if a_edge is None:
-        ge, g_a_dst = _heads_softmax_bwd(g, a_src, a_dst, slope, alpha, galpha, n, nh)
-    else:
-        ge, g_a_dst = _edge_softmax_bwd(g, a_src, a_dst, a_edge, slope, alpha, galpha, n, nh)
-    return gh, _heads_segment_sum(g.bwd.ptr, b2f, ge, n, nh), g_a_dst, ge
-
-
-class _GatHeadsAggregateFn(torch.autograd.Function):
-    """The unfused multi-head aggregation (edge softmax + weighted sum per head, concatenated or averaged over the
-    heads): the sibling of ``_GatAggregateFn``; ``_GatHeadsConvFn`` is the whole layer."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, a_src, a_dst, slope: float, nh: int, mean: bool):
-        h, a_src, a_dst = h.contiguous(), a_src.contiguous(), a_dst.contiguous()
-        c = h.size(1) // nh
-        alpha = _heads_softmax_fwd(g, a_src, a_dst, slope, h.size(0), nh)
-        out = _heads_agg(g.fwd, alpha, h, None, False, mean, nh, c)
-        ctx.g, ctx.slope, ctx.nh, ctx.c, ctx.mean = g, slope, nh, c, mean
-        ctx.save_for_backward(h, a_src, a_dst, alpha)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        h, a_src, a_dst, alpha = ctx.saved_tensors
-        gm = _grad_layout(gout, 0)
-        if ctx.mean:
-            gm = _heads_spread(gm, ctx.nh, ctx.c)
-        gh, g_a_src, g_a_dst, _ = _gat_heads_edge_backward(ctx.g, gm, h, a_src, a_dst, alpha, ctx.slope, ctx.nh, ctx.c)
-        return None, gh, g_a_src, g_a_dst, None, None, None
-
-
-def gat_heads_aggregate(g: GraphIndex, h, a_src, a_dst, slope: float, heads: int, mean: bool = False,
-                        edge_attr=None, edge_m=None, fill_value="mean") -> torch.Tensor:
-    """``h`` [N, H*C], ``a_src`` / ``a_dst`` [N, H] -> [N, H*C], or [N, C] with ``mean`` (PyG ``concat=False``).
-    ``edge_attr`` [E, D] with the folded ``edge_m`` [D, H] (``gat_edge_fold``): the logits' edge-feature term."""
-    h = resolve(h)
-    if h.dim() != 2 or heads < 1 or h.size(1) % heads or a_src.shape != (h.size(0), heads) or a_dst.shape != a_src.shape:
-        raise ValueError("gat_heads_aggregate: h must be [N, H*C] and a_src / a_dst [N, H]")
-    if edge_attr is None:
-        return _GatHeadsAggregateFn.apply(g, h, a_src, a_dst, float(slope), int(heads), bool(mean))
-    edge_attr, fill_mean, fill = _edge_operands(g, edge_attr, edge_m, int(heads), fill_value)
-    return _GatHeadsEdgeAggregateFn.apply(g, h, a_src, a_dst, float(slope), int(heads), bool(mean), edge_attr, edge_m,
-                                          fill_mean, fill)
-
-
-def gat_heads_fused_ok(h: torch.Tensor, heads: int, mean: bool) -> bool:
-    """Widths the row-wise passes of ``gat_heads_conv`` take: ``fused_gnn_ok`` at H*C, and at C - the width of the
-    output, where the mask and the bias gradient are formed - when the heads are averaged."""
-    return fused_gnn_ok(h) and (not mean or fused_gnn_ok(h[:, :h.size(1) // heads]))
-
-
-class _GatHeadsConvFn(torch.autograd.Function):
-    """Everything of a multi-head GATConv layer behind its ``lin`` - ``_GatConvFn`` with H weights per edge: the dot
-    products of all heads in one pass over h, edge softmax, ``act(aggregation + bias)`` (concatenated, or the mean over
-    the heads) as one launch that gathers every neighbour row once; backward: mask + bias gradient in one pass, (mean:
-    the gradient spread to the heads,) transposed aggregation, SDDMM + softmax backward, and the dot products' backward
-    with the two ``[H, C]`` attention gradients in one pass."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool, nh: int, mean: bool):
-        h = h.contiguous()
-        n, f = h.shape
-        c = f // nh
-        a_s, a_d = att_src.reshape(-1).contiguous(), att_dst.reshape(-1).contiguous()
-        a_src, a_dst = _heads_alpha_fwd(h, a_s, a_d, nh, c)
-        alpha = _heads_softmax_fwd(g, a_src, a_dst, slope, n, nh)
-        y = _heads_agg(g.fwd, alpha, h, bias, relu, mean, nh, c)
-        ctx.g, ctx.slope, ctx.relu, ctx.nh, ctx.c, ctx.mean = g, slope, relu, nh, c, mean
-        ctx.params = (att_src, att_dst, bias)
-        ctx.save_for_backward(h, a_src, a_dst, alpha, a_s, a_d, y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        h, a_src, a_dst, alpha, a_s, a_d, y = ctx.saved_tensors
-        g, slope, nh, c = ctx.g, ctx.slope, ctx.nh, ctx.c
-        att_src, att_dst, bias = ctx.params
-        gm, gb = _heads_out_grad(ctx, gy, y, bias)
-        gh, g_a_src, g_a_dst, _ = _gat_heads_edge_backward(g, gm, h, a_src, a_dst, alpha, slope, nh, c)
-        # the attention dot products' backward: gh += ga_src att_src + ga_dst att_dst per head, the two [H, C] gradients
-        pg = _ParamGrads([att_src, att_dst], ctx.needs_input_grad[2:4], h.device)
-        _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh, c, *pg.bufs, pg.direct)
-        gs, gd = pg.done()
-        return None, gh, gs, gd, gb, None, None, None, None
-
-
-def gat_heads_conv(g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool = False, heads: int = 1,
-                   mean: bool = False) -> torch.Tensor:
-    """The layer behind ``lin`` for ``heads`` >= 1 (``h`` [N, H*C], ``att_*`` [1, H, C]; ``gat_heads_fused_ok``)."""
-    h = resolve(h)
-    if h.dim() != 2 or heads < 1 or h.size(1) != att_src.numel() or att_src.numel() % heads:
-        raise ValueError("gat_heads_conv: h must be [N, H*C] and att_src / att_dst [1, H, C]")
-    return _GatHeadsConvFn.apply(g, h, att_src, att_dst, bias, float(slope), bool(relu), int(heads), bool(mean))
-
-
-# --------------------------------------------------------------------------- #
-# GATv2Conv (dc_gatv2.hip): xl = lin_l(x), xr = lin_r(x) [N, H*C]; the logit is per edge, head and channel, so the score
-# and both sides of its backward are gather kernels of their own.  Aggregation, SDDMM, spread and the mask / bias
-# gradient pass are the multi-head launchers above.  One launcher per C entry.
-# --------------------------------------------------------------------------- #
-def _gatv2_softmax_fwd(g: GraphIndex, xl, xr, att, slope: float, nh: int, c: int) -> torch.Tensor:
-    """alpha [capacity, H]: the edge softmax of ``e[p, k] = sum_c att[k, c] leaky_relu(xl[j, k, c] + xr[i, k, c])``."""
-    alpha = _heads_edge_vector(g, nh, xl.device)
-    _lib.check(_lib.lib().dc_gatv2_softmax_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), xl.data_ptr(),
-                                               _rowmajor(xl, "xl"), xr.data_ptr(), _rowmajor(xr, "xr"), att.data_ptr(),
-                                               slope, alpha.data_ptr(), xl.size(0), nh, c, current_stream_ptr(xl.device)),
-               "dc_gatv2_softmax_fwd")
-    return alpha
-
-
-def _gatv2_softmax_bwd(g: GraphIndex, alpha, galpha, xl, xr, att, slope: float, nh: int, c: int, g_att,
-                       accumulate: bool):
-    """-> (ge [capacity, H], g_xr [N, H*C]); ``g_att`` [H*C] is written (``accumulate``: added to)."""
-    n, dev = xl.size(0), xl.device
-    L = _lib.lib()
-    ge = _heads_edge_vector(g, nh, dev)
-    g_xr = torch.empty((n, nh * c), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(L.dc_gatv2_workspace_bytes(n, nh, c), 16), dtype=torch.uint8, device=dev)
-    _lib.check(L.dc_gatv2_softmax_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), alpha.data_ptr(), galpha.data_ptr(),
-                                      xl.data_ptr(), _rowmajor(xl, "xl"), xr.data_ptr(), _rowmajor(xr, "xr"),
-                                      att.data_ptr(), slope, ge.data_ptr(), g_xr.data_ptr(), nh * c, g_att.data_ptr(),
-                                      int(accumulate), ws.data_ptr(), ws.numel(), n, nh, c, current_stream_ptr(dev)),
-               "dc_gatv2_softmax_bwd")
-    return ge, g_xr
-
-
-def _gatv2_source_bwd(g: GraphIndex, alpha, ge, gm, xl, xr, att, slope: float, nh: int, c: int) -> torch.Tensor:
-    """g_xl [N, H*C] over the transposed set: the transposed aggregation of ``gm`` and the score's source term at once."""
-    n, dev = xl.size(0), xl.device
-    g_xl = torch.empty((n, nh * c), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_gatv2_source_bwd(g.bwd.ptr.data_ptr(), g.bwd.other.data_ptr(), g.bwd_to_fwd().data_ptr(),
-                                              alpha.data_ptr(), ge.data_ptr(), gm.data_ptr(), _rowmajor(gm, "gm"),
-                                              xl.data_ptr(), _rowmajor(xl, "xl"), xr.data_ptr(), _rowmajor(xr, "xr"),
-                                              att.data_ptr(), slope, g_xl.data_ptr(), nh * c, n, nh, c,
-                                              current_stream_ptr(dev)), "dc_gatv2_source_bwd")
-    return g_xl
-
-
-class _Gatv2ConvFn(torch.autograd.Function):
-    """Everything of a GATv2Conv layer behind its two linears: score + edge softmax in one launch, then
-    ``act(aggregation of xl + bias)`` (concatenated, or the mean over the heads) as for ``_GatHeadsConvFn``; backward:
-    mask + bias gradient in one pass, (mean: the gradient spread to the heads,) SDDMM, then the destination side (ge,
-    g_xr, g_att) and the source side (g_xl: the transposed aggregation and the score's term in one walk).  With
-    ``bias`` None and ``relu`` False it is the bare aggregation, at every width."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, xl, xr, att, bias, slope: float, relu: bool, nh: int, mean: bool):
-        shared = xl is xr
-        xl = xl.contiguous()
-        xr = xl if shared else xr.contiguous()
-        c = xl.size(1) // nh
-        a = att.reshape(-1).contiguous()
-        alpha = _gatv2_softmax_fwd(g, xl, xr, a, slope, nh, c)
-        y = _heads_agg(g.fwd, alpha, xl, bias, relu, mean, nh, c)
-        ctx.g, ctx.slope, ctx.relu, ctx.nh, ctx.c, ctx.mean = g, slope, relu, nh, c, mean
-        ctx.params = (att, bias)
-        ctx.save_for_backward(xl, xr, alpha, a, y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        xl, xr, alpha, a, y = ctx.saved_tensors
-        g, slope, nh, c = ctx.g, ctx.slope, ctx.nh, ctx.c
-        att, bias = ctx.params
-        gm, gb = _heads_out_grad(ctx, gy, y, bias)
-        galpha = _heads_sddmm(g, gm, xl, nh, c)
-        pg = _ParamGrads([att], ctx.needs_input_grad[3:4], xl.device)
-        ge, g_xr = _gatv2_softmax_bwd(g, alpha, galpha, xl, xr, a, slope, nh, c, pg.bufs[0], pg.direct)
-        g_xl = _gatv2_source_bwd(g, alpha, ge, gm, xl, xr, a, slope, nh, c)
-        (g_att,) = pg.done()
-        return None, g_xl, g_xr, g_att, gb, None, None, None, None
-
-
-def gatv2_conv(g: GraphIndex, xl, xr, att, bias, slope: float, relu: bool = False, heads: int = 1,
-               mean: bool = False) -> torch.Tensor:
-    """The GATv2Conv layer behind ``lin_l`` / ``lin_r`` (``xl`` / ``xr`` [N, H*C] - the same tensor with shared weights -
-    ``att`` [1, H, C]).  With ``bias`` or ``relu`` the widths must pass ``gat_heads_fused_ok`` (the mask / bias-gradient
-    pass); the bare aggregation (``bias`` None, ``relu`` False) runs at every width."""
-    xl, xr = resolve(xl), resolve(xr)
-    if (xl.dim() != 2 or heads < 1 or xl.shape != xr.shape or xl.size(1) != att.numel() or att.numel() % heads):
-        raise ValueError("gatv2_conv: xl / xr must be [N, H*C] and att [1, H, C]")
-    if (bias is not None or relu) and not gat_heads_fused_ok(xl, heads, mean):
-        raise ValueError(f"gatv2_conv: bias / relu need widths the fused row passes take (gat_heads_fused_ok), got "
-                         f"H*C = {xl.size(1)}, H = {heads}; call it without them and apply them outside")
-    return _Gatv2ConvFn.apply(g, xl, xr, att, bias, float(slope), bool(relu), int(heads), bool(mean))
-
-
-# --------------------------------------------------------------------------- #
-# GATConv with edge features (dc_gat_edge.hip; the softmax with the per-edge addend shares dc_gat_heads.hip's templates).
-# The edge term <lin_edge(edge_attr[p])[k, :], att_edge[k, :]> is linear in edge_attr: a_edge = edge_attr @ M with the
-# folded M [D, H] formed by ordinary torch ops OUTSIDE the Functions below, so autograd turns their gM into the
-# gradients of lin_edge.weight and att_edge.  One launcher per C entry.
-# --------------------------------------------------------------------------- #
-GAT_EDGE_MAX_DIM = 64              # DC_GAT_EDGE_MAX_DIM of include/deformcontact.h
-
-
-def gat_edge_fold(lin_edge_weight: torch.Tensor, att_edge: torch.Tensor) -> torch.Tensor:
-    """``M[d, k] = sum_c lin_edge.weight[k C + c, d] att_edge[k, c]`` ([D, H]; differentiable, D*H*C flops)."""
-    _, nh, c = att_edge.shape
-    return (lin_edge_weight.view(nh, c, -1) * att_edge.view(nh, c, 1)).sum(1).t().contiguous()
-
-
-def gat_edge_fill(fill_value):
-    """``fill_value`` of the appended self loops' attribute -> (mean?, constant): ``"mean"`` or a Python number."""
-    if isinstance(fill_value, str):
-        if fill_value != "mean":
-            raise ValueError(f"fill_value must be 'mean' or a float, got {fill_value!r}")
-        return True, 0.0
-    if isinstance(fill_value, bool) or not isinstance(fill_value, (int, float)):
-        raise ValueError(f"fill_value must be 'mean' or a float, got {fill_value!r}")
-    return False, float(fill_value)
-
-
-def _edge_operands(g: GraphIndex, edge_attr, m, nh: int, fill_value):
-    """Checked operands of the edge-feature kernels: ``edge_attr`` float32 [E, D] with inner stride 1 on the graph's
-    device, ``m`` [D, H], the graph a plain self-loop adjacency (its ``perm`` holds this ``edge_index``'s edge ids)."""
-    fill_mean, fill = gat_edge_fill(fill_value)
-    if m is None or m.dim() != 2 or m.size(1) != nh:
-        raise ValueError("edge_m must be the folded [edge_dim, heads] matrix (ops.gat_edge_fold)")
-    d = m.size(0)
-    if not 1 <= d <= GAT_EDGE_MAX_DIM:
-        raise ValueError(f"edge_dim = {d}: the edge-feature kernels take 1 <= edge_dim <= {GAT_EDGE_MAX_DIM}")
-    if not isinstance(g, GraphIndex) or g.parts is not None or not g.self_loops:
-        raise ValueError("edge features need the layer's own self-loop adjacency of this edge_index (not a merged one)")
-    _require_cuda(edge_attr, "edge_attr")
-    if edge_attr.dtype != torch.float32:
-        raise ValueError(f"edge_attr must be float32, got {edge_attr.dtype}")
-    if edge_attr.dim() == 1 and d == 1:
-        edge_attr = edge_attr.unsqueeze(-1)
-    if edge_attr.dim() != 2 or edge_attr.size(1) != d:
-        raise ValueError(f"edge_attr must be [E, {d}] (edge_dim = {d}), got {tuple(edge_attr.shape)}")
-    if edge_attr.size(0) != g.num_input_edges:
-        raise ValueError(f"edge_attr has {edge_attr.size(0)} rows for {g.num_input_edges} edges")
-    if edge_attr.device != g.device:
-        raise RuntimeError(f"edge_attr is on {edge_attr.device} but the graph is on {g.device}")
-    if edge_attr.stride(1) != 1 or (edge_attr.size(0) > 1 and edge_attr.stride(0) < d):
-        edge_attr = edge_attr.contiguous()                       # (a row stride is taken as it is)
-    return edge_attr, fill_mean, fill
-
-
-def _edge_lda(edge_attr) -> int:
-    return edge_attr.stride(0) if edge_attr.size(0) > 1 else edge_attr.size(1)
-
-
-def _edge_term_fwd(g: GraphIndex, edge_attr, m, fill_mean: bool, fill: float, n: int, nh: int):
-    """(a_edge [capacity, H] in ``g.fwd`` order, loop_attr [N, D]: the attribute row of every appended self loop)"""
-    dev, d = m.device, m.size(0)
-    a_edge = _heads_edge_vector(g, nh, dev)
-    loop_attr = torch.empty((n, d), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_gat_edge_attr_fwd(g.fwd.ptr.data_ptr(), g.fwd.perm.data_ptr(), _ptr(edge_attr) or None,
-                                               _edge_lda(edge_attr), m.data_ptr(), int(fill_mean), fill,
-                                               a_edge.data_ptr(), loop_attr.data_ptr(), n, g.num_input_edges, d, nh,
-                                               current_stream_ptr(dev)), "dc_gat_edge_attr_fwd")
-    return a_edge, loop_attr
-
-
-def _edge_softmax_fwd(g: GraphIndex, a_src, a_dst, a_edge, slope: float, n: int, nh: int) -> torch.Tensor:
-    alpha = _heads_edge_vector(g, nh, a_src.device)
-    _lib.check(_lib.lib().dc_gat_edge_attr_softmax_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
-                                                       a_dst.data_ptr(), a_edge.data_ptr(), slope, alpha.data_ptr(), n, nh,
-                                                       current_stream_ptr(a_src.device)), "dc_gat_edge_attr_softmax_fwd")
-    return alpha
-
-
-def _edge_softmax_bwd(g: GraphIndex, a_src, a_dst, a_edge, slope: float, alpha, galpha, n: int, nh: int):
-    dev = alpha.device
-    ge = _heads_edge_vector(g, nh, dev)
-    g_a_dst = torch.empty((n, nh), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_gat_edge_attr_softmax_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), a_src.data_ptr(),
-                                                       a_dst.data_ptr(), a_edge.data_ptr(), slope, alpha.data_ptr(),
-                                                       galpha.data_ptr(), ge.data_ptr(), g_a_dst.data_ptr(), n, nh,
-                                                       current_stream_ptr(dev)), "dc_gat_edge_attr_softmax_bwd")
-    return ge, g_a_dst
-
-
-def _edge_term_bwd(g: GraphIndex, ge, edge_attr, loop_attr, m, fill_mean: bool, n: int, nh: int, need_attr: bool,
-                   need_m: bool):
-    """(g_edge_attr [E, D] or None, gM [D, H] or None) from ``ge``, the gradient of the logits (= of a_edge)."""
-    if not (need_attr or need_m):
-        return None, None
-    L = _lib.lib()
-    dev, d, e = m.device, m.size(0), g.num_input_edges
-    g_attr = torch.empty((e, d), dtype=torch.float32, device=dev) if need_attr else None
-    g_m = torch.empty((d, nh), dtype=torch.float32, device=dev) if need_m else None
-    ws = torch.empty(max(L.dc_gat_edge_attr_bwd_workspace_bytes(g.capacity, d, nh), 16), dtype=torch.uint8, device=dev)
-    _lib.check(L.dc_gat_edge_attr_bwd(g.fwd.ptr.data_ptr(), g.fwd.perm.data_ptr(), ge.data_ptr(), _ptr(edge_attr) or None,
-                                      _edge_lda(edge_attr), loop_attr.data_ptr(), m.data_ptr(), int(fill_mean),
-                                      _ptr(g_attr) or None, d, _ptr(g_m), n, e, d, nh, g.capacity, ws.data_ptr(),
-                                      ws.numel(), current_stream_ptr(dev)), "dc_gat_edge_attr_bwd")
-    return g_attr, g_m
-
-
-class _GatHeadsEdgeAggregateFn(torch.autograd.Function):
-    """``_GatHeadsAggregateFn`` with the edge-feature term in the logits: the unfused aggregation at the widths
-    ``gat_heads_fused_ok`` does not take."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, a_src, a_dst, slope: float, nh: int, mean: bool, edge_attr, m, fill_mean: bool,
-                fill: float):
-        h, a_src, a_dst, m = h.contiguous(), a_src.contiguous(), a_dst.contiguous(), m.contiguous()
-        n, c = h.size(0), h.size(1) // nh
-        a_edge, loop_attr = _edge_term_fwd(g, edge_attr, m, fill_mean, fill, n, nh)
-        alpha = _edge_softmax_fwd(g, a_src, a_dst, a_edge, slope, n, nh)
-        out = _heads_agg(g.fwd, alpha, h, None, False, mean, nh, c)
-        ctx.g, ctx.slope, ctx.nh, ctx.c, ctx.mean, ctx.fill_mean = g, slope, nh, c, mean, fill_mean
-        ctx.save_for_backward(h, a_src, a_dst, alpha, a_edge, loop_attr, edge_attr, m)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        h, a_src, a_dst, alpha, a_edge, loop_attr, edge_attr, m = ctx.saved_tensors
-        gm = _grad_layout(gout, 0)
-        if ctx.mean:
-            gm = _heads_spread(gm, ctx.nh, ctx.c)
-        gh, g_a_src, g_a_dst, ge = _gat_heads_edge_backward(ctx.g, gm, h, a_src, a_dst, alpha, ctx.slope, ctx.nh, ctx.c,
-                                                            a_edge)
-        g_attr, g_m = _edge_term_bwd(ctx.g, ge, edge_attr, loop_attr, m, ctx.fill_mean, h.size(0), ctx.nh,
-                                     ctx.needs_input_grad[7], ctx.needs_input_grad[8])
-        return None, gh, g_a_src, g_a_dst, None, None, None, g_attr, g_m, None, None
-
-
-class _GatHeadsEdgeConvFn(torch.autograd.Function):
-    """``_GatHeadsConvFn`` with the edge-feature term in the logits (every H >= 1): the edge-term launch in front of the
-    softmax, the softmax entries with the per-edge addend, and in backward one more entry for the gradients of
-    ``edge_attr`` (through the loops' mean fill too) and of the folded ``M``."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu: bool, nh: int, mean: bool, edge_attr,
-                m, fill_mean: bool, fill: float):
-        h, m = h.contiguous(), m.contiguous()
-        n, f = h.shape
-        c = f // nh
-        a_s, a_d = att_src.reshape(-1).contiguous(), att_dst.reshape(-1).contiguous()
-        a_src, a_dst = _heads_alpha_fwd(h, a_s, a_d, nh, c)
-        a_edge, loop_attr = _edge_term_fwd(g, edge_attr, m, fill_mean, fill, n, nh)
-        alpha = _edge_softmax_fwd(g, a_src, a_dst, a_edge, slope, n, nh)
-        y = _heads_agg(g.fwd, alpha, h, bias, relu, mean, nh, c)
-        ctx.g, ctx.slope, ctx.relu, ctx.nh, ctx.c, ctx.mean, ctx.fill_mean = g, slope, relu, nh, c, mean, fill_mean
-        ctx.params = (att_src, att_dst, bias)
-        ctx.save_for_backward(h, a_src, a_dst, alpha, a_s, a_d, y if relu else None, a_edge, loop_attr, edge_attr, m)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        h, a_src, a_dst, alpha, a_s, a_d, y, a_edge, loop_attr, edge_attr, m = ctx.saved_tensors
-        g, slope, nh, c = ctx.g, ctx.slope, ctx.nh, ctx.c
-        att_src, att_dst, bias = ctx.params
-        gm, gb = _heads_out_grad(ctx, gy, y, bias)
-        gh, g_a_src, g_a_dst, ge = _gat_heads_edge_backward(g, gm, h, a_src, a_dst, alpha, slope, nh, c, a_edge)
-        g_attr, g_m = _edge_term_bwd(g, ge, edge_attr, loop_attr, m, ctx.fill_mean, h.size(0), nh,
-                                     ctx.needs_input_grad[9], ctx.needs_input_grad[10])
-        pg = _ParamGrads([att_src, att_dst], ctx.needs_input_grad[2:4], h.device)
-        _heads_alpha_bwd(h, g_a_src, g_a_dst, a_s, a_d, gh, nh, c, *pg.bufs, pg.direct)
-        gs, gd = pg.done()
-        return None, gh, gs, gd, gb, None, None, None, None, g_attr, g_m, None, None
-
-
-def gat_heads_edge_conv(g: GraphIndex, h, att_src, att_dst, bias, slope: float, edge_attr, edge_m, relu: bool = False,
-                        heads: int = 1, mean: bool = False, fill_value="mean") -> torch.Tensor:
-    """``gat_heads_conv`` with edge features: ``edge_attr`` [E, D] in the order of the graph's ``edge_index``, ``edge_m``
-    [D, H] = ``gat_edge_fold(lin_edge.weight, att_edge)``; ``fill_value``: the appended self loops' attribute."""
-    h = resolve(h)
-    if h.dim() != 2 or heads < 1 or h.size(1) != att_src.numel() or att_src.numel() % heads:
-        raise ValueError("gat_heads_edge_conv: h must be [N, H*C] and att_src / att_dst [1, H, C]")
-    edge_attr, fill_mean, fill = _edge_operands(g, edge_attr, edge_m, int(heads), fill_value)
-    return _GatHeadsEdgeConvFn.apply(g, h, att_src, att_dst, bias, float(slope), bool(relu), int(heads), bool(mean),
-                                     edge_attr, edge_m, fill_mean, fill)
-
-
-# --------------------------------------------------------------------------- #
 # the two training losses in one pass (train.py:51-53, models/losses.py:7-19)
 # --------------------------------------------------------------------------- #
 class _ContactLossFn(torch.autograd.Function):
@@ -1952,514 +1230,12 @@ def contact_losses(g: GraphIndex, pred_pos: torch.Tensor, target_pos: torch.Tens
 
 
 # --------------------------------------------------------------------------- #
-# TransformerConv (dc_transformer.hip): q = lin_query(x), k = lin_key(x), v = lin_value(x) [N, H*C]; the logit is the
-# scaled dot product <q_i, k_j> / sqrt(C) per edge and head.  Score + edge softmax and both sides of the backward are
-# gather kernels of their own; aggregation, SDDMM, spread and the mask / bias gradient pass are the multi-head
-# launchers above.  One launcher per C entry.
+# The other layers: their code is in ``layers/``, their switches and their public names are here
 # --------------------------------------------------------------------------- #
-def _tconv_scale(c: int) -> float:
-    """``float32(1 / sqrt(C))`` (the C entries take a float: ctypes rounds the double to nearest)"""
-    return 1.0 / float(c) ** 0.5
+#: GCNConv / GATConv: aggregation + bias + ReLU as one node, row-wise passes fused (dc_gnn_epi.hip; read by
+#: ``fused_gnn_ok``).  False: the unfused layer composition - tests compare the two
+FUSED_GNN_EPILOGUE = True
 
-
-def _tconv_softmax_fwd(g: GraphIndex, q, k, nh: int, c: int) -> torch.Tensor:
-    """alpha [capacity, H]: the edge softmax of ``e[p, h] = <q[i, h, :], k[j, h, :]> / sqrt(C)``."""
-    alpha = _heads_edge_vector(g, nh, q.device)
-    _lib.check(_lib.lib().dc_tconv_softmax_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), q.data_ptr(),
-                                               _rowmajor(q, "q"), k.data_ptr(), _rowmajor(k, "k"), _tconv_scale(c),
-                                               alpha.data_ptr(), q.size(0), nh, c, current_stream_ptr(q.device)),
-               "dc_tconv_softmax_fwd")
-    return alpha
-
-
-def _tconv_softmax_bwd(g: GraphIndex, alpha, galpha, k, nh: int, c: int):
-    """-> (gl [capacity, H], the gradient of the dot products; g_q [N, H*C])"""
-    n, dev = k.size(0), k.device
-    gl = _heads_edge_vector(g, nh, dev)
-    g_q = torch.empty((n, nh * c), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_tconv_softmax_bwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), alpha.data_ptr(),
-                                               galpha.data_ptr(), k.data_ptr(), _rowmajor(k, "k"), _tconv_scale(c),
-                                               gl.data_ptr(), g_q.data_ptr(), nh * c, n, nh, c,
-                                               current_stream_ptr(dev)), "dc_tconv_softmax_bwd")
-    return gl, g_q
-
-
-def _tconv_source_bwd(g: GraphIndex, alpha, gl, q, gm, nh: int, c: int):
-    """-> (g_k, g_v) [N, H*C] over the transposed set: the score's key term and the transposed aggregation in one walk."""
-    n, dev = q.size(0), q.device
-    g_k = torch.empty((n, nh * c), dtype=torch.float32, device=dev)
-    g_v = torch.empty((n, nh * c), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().dc_tconv_source_bwd(g.bwd.ptr.data_ptr(), g.bwd.other.data_ptr(), g.bwd_to_fwd().data_ptr(),
-                                              alpha.data_ptr(), gl.data_ptr(), q.data_ptr(), _rowmajor(q, "q"),
-                                              gm.data_ptr(), _rowmajor(gm, "gm"), g_k.data_ptr(), nh * c, g_v.data_ptr(),
-                                              nh * c, n, nh, c, current_stream_ptr(dev)), "dc_tconv_source_bwd")
-    return g_k, g_v
-
-
-class _TransformerAggFn(torch.autograd.Function):
-    """The attention of a TransformerConv layer behind its three linears: score + edge softmax in one launch, then
-    ``act(aggregation of v + bias)`` (concatenated, or the mean over the heads) as for ``_Gatv2ConvFn``; backward: mask
-    + bias gradient in one pass (only with ``relu`` / ``bias``), (mean: the gradient spread to the heads,) SDDMM, then
-    the destination side (gl, g_q) and the source side (g_k, g_v in one walk).  The node ends at the aggregation: the
-    skip connection and the gate are the layer's."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, q, k, v, bias, relu: bool, nh: int, mean: bool):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        n, c = q.size(0), q.size(1) // nh
-        ctx.g, ctx.relu, ctx.nh, ctx.c, ctx.mean, ctx.bias = g, relu, nh, c, mean, bias
-        ctx.empty = n == 0
-        if ctx.empty:                        # no rows: nothing to launch (an empty tensor has no address)
-            return q.new_empty((0, c if mean else nh * c))
-        alpha = _tconv_softmax_fwd(g, q, k, nh, c)
-        y = _heads_agg(g.fwd, alpha, v, bias, relu, mean, nh, c)
-        ctx.save_for_backward(q, k, v, alpha, y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        g, nh, c, bias = ctx.g, ctx.nh, ctx.c, ctx.bias
-        need_b = bias is not None and ctx.needs_input_grad[4]
-        if ctx.empty:                        # sums over no rows
-            z = gy.new_zeros((0, nh * c))
-            return None, z, z, z, (gy.new_zeros(gy.size(1)) if need_b else None), None, None, None
-        q, k, v, alpha, y = ctx.saved_tensors
-        gm, gb = _heads_out_grad(ctx, gy, y, bias)
-        galpha = _heads_sddmm(g, gm, v, nh, c)
-        gl, g_q = _tconv_softmax_bwd(g, alpha, galpha, k, nh, c)
-        g_k, g_v = _tconv_source_bwd(g, alpha, gl, q, gm, nh, c)
-        return None, g_q, g_k, g_v, gb, None, None, None
-
-
-def transformer_conv(g: GraphIndex, q, k, v, bias=None, relu: bool = False, heads: int = 1,
-                     mean: bool = False) -> torch.Tensor:
-    """The attention of a TransformerConv layer behind ``lin_query`` / ``lin_key`` / ``lin_value`` (``q`` / ``k`` / ``v``
-    [N, H*C]) on the edge set of ``g`` as it is: [N, H*C], or [N, C] with ``mean``; a row without edges is 0 (+ bias).
-    With ``bias`` or ``relu`` the widths must pass ``gat_heads_fused_ok`` (the mask / bias-gradient pass); the bare
-    aggregation runs at every width."""
-    q, k, v = resolve(q), resolve(k), resolve(v)
-    if q.dim() != 2 or heads < 1 or q.size(1) % heads or q.size(1) == 0 or k.shape != q.shape or v.shape != q.shape:
-        raise ValueError("transformer_conv: q / k / v must be [N, H*C]")
-    if (bias is not None or relu) and not gat_heads_fused_ok(v, heads, mean):
-        raise ValueError(f"transformer_conv: bias / relu need widths the fused row passes take (gat_heads_fused_ok), got "
-                         f"H*C = {q.size(1)}, H = {heads}; call it without them and apply them outside")
-    return _TransformerAggFn.apply(g, q, k, v, bias, bool(relu), int(heads), bool(mean))
-
-
-# --------------------------------------------------------------------------- #
-# SAGEConv (dc_sage.hip): the mean and the max over a node's in-edges on the edge set as it is given.  Segment
-# reductions over the sorted adjacency, their backward over the transposed set; the sum is the unweighted hop.  One
-# launcher per C entry.
-# --------------------------------------------------------------------------- #
-def _sage_mean_fwd(g: GraphIndex, x) -> torch.Tensor:
-    """y [N, F]: the hop's sum over the in-edges divided by the in-degree; 0 for a row without edges."""
-    n, f = x.shape
-    y = torch.empty((n, f), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().dc_sage_mean_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), x.data_ptr(), _rowmajor(x, "x"),
-                                           y.data_ptr(), f, n, f, current_stream_ptr(x.device)), "dc_sage_mean_fwd")
-    return y
-
-
-def _sage_mean_bwd(g: GraphIndex, gy) -> torch.Tensor:
-    """g_x [N, F] over the transposed set: ``sum g_y[i] / deg_i``, the in-degree read from the forward ``ptr``."""
-    n, f = gy.shape
-    gx = torch.empty((n, f), dtype=torch.float32, device=gy.device)
-    _lib.check(_lib.lib().dc_sage_mean_bwd(g.bwd.ptr.data_ptr(), g.bwd.other.data_ptr(), g.fwd.ptr.data_ptr(),
-                                           gy.data_ptr(), _rowmajor(gy, "gy"), gx.data_ptr(), f, n, f,
-                                           current_stream_ptr(gy.device)), "dc_sage_mean_bwd")
-    return gx
-
-
-def _sage_max_fwd(g: GraphIndex, x, want_cnt: bool):
-    """-> (m [N, F], cnt int32 [N, F] or None): the maximum over the in-edges and the number of edges that attain it."""
-    n, f = x.shape
-    m = torch.empty((n, f), dtype=torch.float32, device=x.device)
-    cnt = torch.empty((n, f), dtype=torch.int32, device=x.device) if want_cnt else None
-    _lib.check(_lib.lib().dc_sage_max_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), x.data_ptr(), _rowmajor(x, "x"),
-                                          m.data_ptr(), f, _ptr(cnt), f, n, f, current_stream_ptr(x.device)),
-               "dc_sage_max_fwd")
-    return m, cnt
-
-
-def _sage_max_bwd(g: GraphIndex, x, m, cnt, gm) -> torch.Tensor:
-    """g_x [N, F] over the transposed set: the gradient of every maximum split evenly among the edges that attain it."""
-    n, f = x.shape
-    gx = torch.empty((n, f), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().dc_sage_max_bwd(g.bwd.ptr.data_ptr(), g.bwd.other.data_ptr(), x.data_ptr(), _rowmajor(x, "x"),
-                                          m.data_ptr(), _rowmajor(m, "m"), cnt.data_ptr(),
-                                          _rowmajor(cnt, "cnt", (torch.int32,)), gm.data_ptr(), _rowmajor(gm, "gm"),
-                                          gx.data_ptr(), f, n, f, current_stream_ptr(x.device)), "dc_sage_max_bwd")
-    return gx
-
-
-def _sage_grad(g: torch.Tensor) -> torch.Tensor:
-    """The incoming gradient with unit inner stride and rows that do not overlap (an expanded one is copied)."""
-    g = _grad_layout(g, 1)
-    return g if g.size(0) <= 1 or g.stride(0) >= g.size(1) else g.contiguous()
-
-
-class _SageMeanFn(torch.autograd.Function):
-    """``mean`` over the in-edges: one launch forward, one backward; nothing is saved but the graph."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, x):
-        ctx.g, ctx.empty = g, x.size(0) == 0
-        if ctx.empty:                        # no rows: nothing to launch (an empty tensor has no address)
-            return x.new_empty(x.shape)
-        return _sage_mean_fwd(g, x)
-
-    @staticmethod
-    def backward(ctx, gy):
-        if ctx.empty:
-            return None, gy.new_zeros(gy.shape)
-        return None, _sage_mean_bwd(ctx.g, _sage_grad(gy))
-
-
-class _SageMaxFn(torch.autograd.Function):
-    """``max`` over the in-edges; with a gradient wanted the forward also stores the tie counts, and x, m, cnt are
-    saved for the even split of the backward."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, x):
-        ctx.g, ctx.empty = g, x.size(0) == 0
-        if ctx.empty:
-            return x.new_empty(x.shape)
-        m, cnt = _sage_max_fwd(g, x, ctx.needs_input_grad[1])
-        if cnt is not None:
-            ctx.save_for_backward(x, m, cnt)
-        return m
-
-    @staticmethod
-    def backward(ctx, gm):
-        if ctx.empty:
-            return None, gm.new_zeros(gm.shape)
-        x, m, cnt = ctx.saved_tensors
-        return None, _sage_max_bwd(ctx.g, x, m, cnt, _sage_grad(gm))
-
-
-def aggregate(g: Optional[GraphIndex], x: torch.Tensor, reduce: str = "mean") -> torch.Tensor:
-    """``reduce`` (``"sum"`` / ``"mean"`` / ``"max"``) of ``x[j]`` over the edges ``j -> i`` of ``g`` - a ``GraphIndex``
-    built with ``self_loops=False, normalize=False``: the edge set as given, duplicates counting - per destination ``i``;
-    a row without edges is 0.  ``"sum"`` is ``propagate(g, x, weighted=False)``; ``"mean"`` is that sum divided by the
-    in-degree in the same launch; ``"max"`` sends the gradient of every maximum in equal shares to ALL edges that
-    attain it.  ``x``: float32 ``[N, F]`` on the graph's device, unit inner stride (a column slice
-    passes as it is).  ``N = 0`` returns an empty tensor without a launch (``g`` may then be None)."""
-    if not isinstance(reduce, str) or reduce not in ("sum", "mean", "max"):
-        raise ValueError(f"aggregate: reduce must be 'sum', 'mean' or 'max', got {reduce!r}")
-    x = resolve(x)
-    _require_cuda(x, "x")
-    if x.dim() != 2 or x.dtype != torch.float32 or x.size(1) == 0:
-        raise ValueError(f"aggregate: x must be a float32 [N, F >= 1] tensor, got {tuple(x.shape)} {x.dtype}")
-    if x.size(0) == 0:
-        return _SageMeanFn.apply(None, x)
-    if g is None:
-        raise ValueError("aggregate: g may be None only for an x without rows")
-    if g.self_loops or g.normalize:
-        raise ValueError("aggregate: the graph must be built with self_loops=False, normalize=False")
-    if g.device != x.device:
-        raise RuntimeError(f"aggregate: x is on {x.device} but the graph is on {g.device}")
-    if g.num_nodes != x.size(0):
-        raise ValueError(f"aggregate: x has {x.size(0)} rows but the graph has {g.num_nodes} nodes")
-    if reduce == "sum":
-        return propagate(g, x, weighted=False)
-    if x.size(1) > 1 and x.stride(1) != 1:
-        x = x.contiguous()
-    return (_SageMeanFn if reduce == "mean" else _SageMaxFn).apply(g, x)
-
-
-# --------------------------------------------------------------------------- #
-# GINEConv (dc_gine.hip): (1 + eps) x_i + the sum over the in-edges of relu(x_j + e_ji) on the edge set as it is given,
-# e [E, F] in the order of the input edges (read through the adjacency's ``perm``).  The backward recomputes the ReLU
-# mask from x and e.  One launcher per C entry.
-# --------------------------------------------------------------------------- #
-def _gine_fwd(g: GraphIndex, x, e, eps) -> torch.Tensor:
-    """y [N, F]: ``(1 + eps) x[i] + sum_p max(x[other[p]] + e[perm[p]], 0)`` in p order; ``eps`` None: no root term."""
-    n, f = x.shape
-    y = torch.empty((n, f), dtype=torch.float32, device=x.device)
-    if e.size(0) == 0:
-        e = x                                # no edge: e has no address, and the kernel reads it per edge only
-    _lib.check(_lib.lib().dc_gine_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), g.fwd.perm.data_ptr(), x.data_ptr(),
-                                      _rowmajor(x, "x"), e.data_ptr(), _rowmajor(e, "e"), _ptr(eps), y.data_ptr(), f,
-                                      n, f, current_stream_ptr(x.device)), "dc_gine_fwd")
-    return y
-
-
-def _gine_bwd_x(g: GraphIndex, x, e, eps, gy) -> torch.Tensor:
-    """g_x [N, F] over the transposed set: ``(1 + eps) g_y[j] + sum_t (x[j] + e[perm_t[t]] > 0) g_y[other_t[t]]``."""
-    n, f = x.shape
-    gx = torch.empty((n, f), dtype=torch.float32, device=x.device)
-    if e.size(0) == 0:
-        e = x
-    _lib.check(_lib.lib().dc_gine_bwd_x(g.bwd.ptr.data_ptr(), g.bwd.other.data_ptr(), g.bwd.perm.data_ptr(),
-                                        x.data_ptr(), _rowmajor(x, "x"), e.data_ptr(), _rowmajor(e, "e"), _ptr(eps),
-                                        gy.data_ptr(), _rowmajor(gy, "gy"), gx.data_ptr(), f, n, f,
-                                        current_stream_ptr(x.device)), "dc_gine_bwd_x")
-    return gx
-
-
-def _gine_bwd_e(g: GraphIndex, x, e, gy) -> torch.Tensor:
-    """g_e [E, F] in the order of the input edges: ``(x[src_q] + e[q] > 0) g_y[dst_q]``, every row written once."""
-    n, f = x.shape
-    ne = e.size(0)
-    ge = torch.empty((ne, f), dtype=torch.float32, device=x.device)
-    if ne == 0:
-        return ge
-    ei = g.edge_index
-    _lib.check(_lib.lib().dc_gine_bwd_e(ei[0].data_ptr(), ei[1].data_ptr(), x.data_ptr(), _rowmajor(x, "x"),
-                                        e.data_ptr(), _rowmajor(e, "e"), gy.data_ptr(), _rowmajor(gy, "gy"),
-                                        ge.data_ptr(), f, n, ne, f, current_stream_ptr(x.device)), "dc_gine_bwd_e")
-    return ge
-
-
-class _GineAggFn(torch.autograd.Function):
-    """``(1 + eps) x_i + sum relu(x_j + e_ji)``: one launch forward; backward one launch for g_x, one for g_e (skipped
-    when e needs no gradient) and a torch reduction ``sum(g_y * x)`` for a trained eps.  Saved: x, e, eps - the ReLU
-    mask is recomputed."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, x, e, eps):
-        ctx.g, ctx.empty = g, x.size(0) == 0
-        if ctx.empty:                        # no rows: nothing to launch (an empty tensor has no address)
-            return x.new_empty(x.shape)
-        ctx.save_for_backward(x, e, eps)
-        return _gine_fwd(g, x, e, eps)
-
-    @staticmethod
-    def backward(ctx, gy):
-        need = ctx.needs_input_grad
-        if ctx.empty:
-            return (None, gy.new_zeros(gy.shape) if need[1] else None, gy.new_zeros(gy.shape) if need[2] else None,
-                    gy.new_zeros(1) if need[3] else None)
-        x, e, eps = ctx.saved_tensors
-        gy = _sage_grad(gy)
-        gx = _gine_bwd_x(ctx.g, x, e, eps, gy) if need[1] else None
-        ge = _gine_bwd_e(ctx.g, x, e, gy) if need[2] else None
-        geps = (gy * x).sum().reshape(1) if need[3] else None
-        return None, gx, ge, geps
-
-
-def gine_aggregate(g: Optional[GraphIndex], x: torch.Tensor, e: torch.Tensor,
-                   eps: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``(1 + eps) x_i + sum_{j->i} relu(x_j + e_ji)`` over the edges of ``g`` - a ``GraphIndex`` of one ``edge_index``
-    built with ``self_loops=False, normalize=False``: the edge set as given, duplicates counting; a row without edges
-    is ``(1 + eps) x_i``.  ``x``: float32 ``[N, F]``; ``e``: float32 ``[E, F]`` with rows in the order of that
-    ``edge_index``; both on the graph's device with unit inner stride (column slices pass as they are).  ``eps``: a
-    float32 ``[1]`` tensor on the same device, read BY THE KERNEL (a parameter changed in place between two replays of
-    a captured step is followed); None: no root term.  One autograd node, differentiable in ``x``, ``e`` and - when it
-    requires a gradient - ``eps``; ``relu'(0) = 0``.  The gradient of ``e`` reads the endpoints
-    from ``g.edge_index`` at backward time while the forward read the sorted set built from it: the edge list must stay
-    unchanged until the backward has run.  ``N = 0`` returns an empty tensor without
-    a launch (``g`` may then be None)."""
-    x, e = resolve(x), resolve(e)
-    _require_cuda(x, "x")
-    _require_cuda(e, "e")
-    if x.dim() != 2 or x.dtype != torch.float32 or x.size(1) == 0:
-        raise ValueError(f"gine_aggregate: x must be a float32 [N, F >= 1] tensor, got {tuple(x.shape)} {x.dtype}")
-    if e.dim() != 2 or e.dtype != torch.float32 or e.size(1) != x.size(1):
-        raise ValueError(f"gine_aggregate: e must be a float32 [E, {x.size(1)}] tensor, got {tuple(e.shape)} {e.dtype}")
-    if e.device != x.device:
-        raise RuntimeError(f"gine_aggregate: x is on {x.device} but e is on {e.device}")
-    if eps is not None:
-        if not isinstance(eps, torch.Tensor) or eps.dtype != torch.float32 or eps.numel() != 1:
-            raise ValueError("gine_aggregate: eps must be a float32 tensor of one element (or None)")
-        if eps.device != x.device:
-            raise RuntimeError(f"gine_aggregate: x is on {x.device} but eps is on {eps.device}")
-    if x.size(0) == 0:
-        if e.size(0) != 0:
-            raise ValueError(f"gine_aggregate: e has {e.size(0)} rows but x has no node")
-        return _GineAggFn.apply(None, x, e, eps)
-    if g is None:
-        raise ValueError("gine_aggregate: g may be None only for an x without rows")
-    if g.self_loops or g.normalize or g.edge_index is None or g.fwd.row_offset or g.bwd.row_offset:
-        raise ValueError("gine_aggregate: the graph must be built from one edge_index with self_loops=False, "
-                         "normalize=False (not a merged adjacency or a row window of one)")
-    if g.device != x.device:
-        raise RuntimeError(f"gine_aggregate: x is on {x.device} but the graph is on {g.device}")
-    if g.num_nodes != x.size(0):
-        raise ValueError(f"gine_aggregate: x has {x.size(0)} rows but the graph has {g.num_nodes} nodes")
-    if g.num_input_edges != e.size(0):
-        raise ValueError(f"gine_aggregate: e has {e.size(0)} rows but the graph has {g.num_input_edges} edges")
-    # unit inner stride and rows that do not overlap (an expanded operand is copied); a column slice passes as it is
-    if (x.size(1) > 1 and x.stride(1) != 1) or (x.size(0) > 1 and x.stride(0) < x.size(1)):
-        x = x.contiguous()
-    if (e.size(1) > 1 and e.stride(1) != 1) or (e.size(0) > 1 and e.stride(0) < e.size(1)):
-        e = e.contiguous()
-    return _GineAggFn.apply(g, x, e, eps)
-
-
-# --------------------------------------------------------------------------- #
-# Per-edge primitives (dc_edge.hip): the pair rows [x_i, x_j - x_i] of every input edge, and the reduction per
-# destination of rows that live on the edges - what a "module per edge" layer (EdgeConv) puts around the user's module.
-# Edge rows are in the order of the input edges; the per-edge kernels read the endpoints from ``g.edge_index``, the
-# per-node kernels walk the sorted sets through their ``perm``.  One launcher per C entry.
-# --------------------------------------------------------------------------- #
-EDGE_REDUCE_MODES = {"sum": 0, "mean": 1, "max": 2}
-
-
-def _edge_pair_fwd(g: GraphIndex, x) -> torch.Tensor:
-    """z [E, 2F] in the order of the input edges: ``[x[dst_q], x[src_q] - x[dst_q]]``, every row written once."""
-    n, f = x.shape
-    ne = g.num_input_edges
-    z = torch.empty((ne, 2 * f), dtype=torch.float32, device=x.device)
-    ei = g.edge_index
-    _lib.check(_lib.lib().dc_edge_pair_fwd(ei[0].data_ptr(), ei[1].data_ptr(), x.data_ptr(), _rowmajor(x, "x"),
-                                           z.data_ptr(), 2 * f, n, ne, f, current_stream_ptr(x.device)),
-               "dc_edge_pair_fwd")
-    return z
-
-
-def _edge_pair_bwd(g: GraphIndex, gz) -> torch.Tensor:
-    """g_x [N, F]: per node the compensated sum of ``g_z[q, :F] - g_z[q, F:]`` over its in-edges, then of
-    ``g_z[q, F:]`` over its out-edges."""
-    n, f = g.num_nodes, gz.size(1) // 2
-    gx = torch.empty((n, f), dtype=torch.float32, device=gz.device)
-    _lib.check(_lib.lib().dc_edge_pair_bwd(g.fwd.ptr.data_ptr(), g.fwd.perm.data_ptr(), g.bwd.ptr.data_ptr(),
-                                           g.bwd.perm.data_ptr(), gz.data_ptr(), _rowmajor(gz, "gz"), gx.data_ptr(), f,
-                                           n, f, current_stream_ptr(gz.device)), "dc_edge_pair_bwd")
-    return gx
-
-
-def _edge_reduce_fwd(g: GraphIndex, m, mode: int, n: Optional[int] = None):
-    """-> (y [N, C], cnt int32 [N, C] for the max, else None): sum / mean / max of the edge rows per destination.
-    ``n``: reduce the first ``n`` rows of the adjacency alone (the destinations of a bipartite set; default: all)."""
-    n, c = g.num_nodes if n is None else n, m.size(1)
-    y = torch.empty((n, c), dtype=torch.float32, device=m.device)
-    cnt = torch.empty((n, c), dtype=torch.int32, device=m.device) if mode == 2 else None
-    _lib.check(_lib.lib().dc_edge_reduce_fwd(g.fwd.ptr.data_ptr(), g.fwd.perm.data_ptr(), m.data_ptr(),
-                                             _rowmajor(m, "m"), y.data_ptr(), c, _ptr(cnt), c, mode, n, c,
-                                             current_stream_ptr(m.device)), "dc_edge_reduce_fwd")
-    return y, cnt
-
-
-def _edge_reduce_bwd(g: GraphIndex, m, y, cnt, gy, mode: int) -> torch.Tensor:
-    """g_m [E, C] in the order of the input edges, every row written once; ``m``, ``y``, ``cnt``: the max only."""
-    n, c = gy.shape
-    ne = g.num_input_edges
-    gm = torch.empty((ne, c), dtype=torch.float32, device=gy.device)
-    ei = g.edge_index
-    saved = [m.data_ptr(), _rowmajor(m, "m"), y.data_ptr(), _rowmajor(y, "y"), cnt.data_ptr(),
-             _rowmajor(cnt, "cnt", (torch.int32,))] if mode == 2 else [None, c, None, c, None, c]
-    _lib.check(_lib.lib().dc_edge_reduce_bwd(ei[0].data_ptr(), ei[1].data_ptr(), g.fwd.ptr.data_ptr(), *saved,
-                                             gy.data_ptr(), _rowmajor(gy, "gy"), gm.data_ptr(), c, mode, n, ne, c,
-                                             current_stream_ptr(gy.device)), "dc_edge_reduce_bwd")
-    return gm
-
-
-class _EdgePairFn(torch.autograd.Function):
-    """``[x_i, x_j - x_i]`` per input edge: one launch forward, one backward; nothing is saved but the graph."""
-
-    @staticmethod
-    def forward(ctx, g: Optional[GraphIndex], x):
-        ne = g.num_input_edges if g is not None else 0
-        ctx.g, ctx.empty = g, ne == 0 or x.size(0) == 0
-        if ctx.empty:                        # no edge or no node: nothing to launch (an empty tensor has no address)
-            return x.new_empty((ne, 2 * x.size(1)))
-        return _edge_pair_fwd(g, x)
-
-    @staticmethod
-    def backward(ctx, gz):
-        if ctx.empty:
-            return None, gz.new_zeros((ctx.g.num_nodes if ctx.g is not None else 0, gz.size(1) // 2))
-        return None, _edge_pair_bwd(ctx.g, _sage_grad(gz))
-
-
-class _EdgeReduceFn(torch.autograd.Function):
-    """``sum`` / ``mean`` / ``max`` of edge rows per destination: one launch forward, one backward.  The max saves m,
-    y and cnt for the even split of the backward; sum and mean save nothing but the graph."""
-
-    @staticmethod
-    def forward(ctx, g: Optional[GraphIndex], m, mode: int):
-        n = g.num_nodes if g is not None else 0
-        ctx.g, ctx.mode, ctx.empty = g, mode, n == 0 or m.size(0) == 0
-        if ctx.empty:                        # no edge: every row is 0; no node: no row
-            return m.new_zeros((n, m.size(1)))
-        y, cnt = _edge_reduce_fwd(g, m, mode)
-        if mode == 2:
-            ctx.save_for_backward(m, y, cnt)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        if ctx.empty:
-            return None, gy.new_zeros((ctx.g.num_input_edges if ctx.g is not None else 0, gy.size(1))), None
-        m, y, cnt = ctx.saved_tensors if ctx.mode == 2 else (None, None, None)
-        return None, _edge_reduce_bwd(ctx.g, m, y, cnt, _sage_grad(gy), ctx.mode), None
-
-
-def _edge_graph_check(who: str, g: GraphIndex, t: torch.Tensor, what: str) -> None:
-    if g.self_loops or g.normalize or g.edge_index is None or g.fwd.row_offset or g.bwd.row_offset:
-        raise ValueError(f"{who}: the graph must be built from one edge_index with self_loops=False, "
-                         "normalize=False (not a merged adjacency or a row window of one)")
-    if g.device != t.device:
-        raise RuntimeError(f"{who}: {what} is on {t.device} but the graph is on {g.device}")
-
-
-def _edge_rows(t: torch.Tensor) -> torch.Tensor:
-    """unit inner stride and rows that do not overlap (an expanded operand is copied); a column slice passes as it is"""
-    if (t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)):
-        return t.contiguous()
-    return t
-
-
-def edge_pairs(g: Optional[GraphIndex], x: torch.Tensor) -> torch.Tensor:
-    """``z [E, 2F]`` with ``z[q] = [x[i], x[j] - x[i]]`` for every edge ``q = (j -> i)`` of ``g``, rows in the order of
-    the ``edge_index`` the graph was built from - the per-edge input of PyG's ``EdgeConv``.  ``g``: a ``GraphIndex`` of
-    one ``edge_index`` built with ``self_loops=False, normalize=False`` (the edge set as given, duplicates counting).
-    ``x``: float32 ``[N, F >= 1]`` on the graph's device with unit inner stride (a column slice passes as it is).  One
-    autograd node; the backward sums per node in a fixed order without float atomics and reads
-    nothing but the graph.  The forward reads the endpoints from ``g.edge_index`` while the backward walks the sorted
-    set built from it: the edge list must stay unchanged until the backward has run.  ``E = 0`` or ``N = 0`` returns
-    an empty ``[E, 2F]`` tensor without a launch (``g`` may be None when ``N = 0``)."""
-    x = resolve(x)
-    _require_cuda(x, "x")
-    if x.dim() != 2 or x.dtype != torch.float32 or x.size(1) == 0:
-        raise ValueError(f"edge_pairs: x must be a float32 [N, F >= 1] tensor, got {tuple(x.shape)} {x.dtype}")
-    if g is None:
-        if x.size(0) != 0:
-            raise ValueError("edge_pairs: g may be None only for an x without rows")
-        return _EdgePairFn.apply(None, x)
-    _edge_graph_check("edge_pairs", g, x, "x")
-    if g.num_nodes != x.size(0):
-        raise ValueError(f"edge_pairs: x has {x.size(0)} rows but the graph has {g.num_nodes} nodes")
-    return _EdgePairFn.apply(g, _edge_rows(x))
-
-
-def edge_aggregate(g: Optional[GraphIndex], m: torch.Tensor, reduce: str = "max") -> torch.Tensor:
-    """``reduce`` (``"sum"`` / ``"mean"`` / ``"max"``) per destination ``i`` of the rows ``m[q]`` that live on the edges
-    ``q = (j -> i)`` of ``g`` -> ``[N, C]``; a node without in-edges gets 0.  ``m``: float32 ``[E, C >= 1]`` with rows
-    in the order of the ``edge_index`` the graph was built from (``E = g.num_input_edges``), on the graph's device,
-    unit inner stride (a column slice passes as it is).  ``g`` as for ``edge_pairs``.  The sum is a plain fp32 sum in
-    the order of the sorted set, the mean that sum divided by the in-degree; ``"max"`` sends the gradient of every
-    maximum in equal shares to ALL edges that attain it, a duplicate edge counting as an edge (INTEGRATION.md 1.5,
-    1.10).  One autograd node; the backward writes every row of the gradient once and reads the endpoints from
-    ``g.edge_index``: the edge list must stay unchanged until the backward has run.  ``N = 0``: ``g`` may be None and
-    the result is an empty ``[0, C]`` tensor; nothing is launched for ``E = 0`` either."""
-    if not isinstance(reduce, str) or reduce not in EDGE_REDUCE_MODES:
-        raise ValueError(f"edge_aggregate: reduce must be 'sum', 'mean' or 'max', got {reduce!r}")
-    m = resolve(m)
-    _require_cuda(m, "m")
-    if m.dim() != 2 or m.dtype != torch.float32 or m.size(1) == 0:
-        raise ValueError(f"edge_aggregate: m must be a float32 [E, C >= 1] tensor, got {tuple(m.shape)} {m.dtype}")
-    mode = EDGE_REDUCE_MODES[reduce]
-    if g is None:
-        if m.size(0) != 0:
-            raise ValueError("edge_aggregate: g may be None only for an m without rows (a graph without nodes)")
-        return _EdgeReduceFn.apply(None, m, mode)
-    _edge_graph_check("edge_aggregate", g, m, "m")
-    if g.num_input_edges != m.size(0):
-        raise ValueError(f"edge_aggregate: m has {m.size(0)} rows but the graph has {g.num_input_edges} edges")
-    return _EdgeReduceFn.apply(g, _edge_rows(m), mode)
-
-
-# --------------------------------------------------------------------------- #
-# PointNetConv (dc_pointnet.hip): the per-edge primitives on a BIPARTITE edge set - sources ``x_src`` / ``pos_src`` with
-# ``Ns`` rows, destinations ``pos_dst`` with ``Nd`` rows - what PointNet++'s set-abstraction layer puts around the
-# user's modules.  The adjacency is ONE ``GraphIndex`` over ``max(Ns, Nd)`` rows (``pointnet_graph``): rows beyond
-# ``Nd`` (by destination) or ``Ns`` (by source) are empty, and the kernels are told the two counts.  With ``loops`` (one
-# node set, an adjacency built with ``self_loops=True``) the edge rows are ``E' = E + N``: input edges in input order,
-# then node ``i``'s loop at row ``E + i``; an input edge with ``src == dst`` keeps its row and takes no part.  The
-# forward reduction is ``dc_edge_reduce_fwd`` as it stands.  One launcher per C entry.
-# --------------------------------------------------------------------------- #
 #: ``pointnet_pairs`` lays ``z`` out with its row stride rounded up to 4 floats where that gives the pair kernel 16-byte
 #: stores (F % 4 == 0, F > 0: one padding column, written as zeros; ``z`` is then a NON-CONTIGUOUS ``[E', F + 3]`` view of
 #: ``[E', F + 4]`` rows - a user's module that calls ``.view()`` on it must call ``.contiguous()`` first); contiguous
@@ -2468,760 +1244,42 @@ def edge_aggregate(g: Optional[GraphIndex], m: torch.Tensor, reduce: str = "max"
 #: the strided operand; at F = 3 (6 columns, 8 padded) the two layouts tie, so nothing is padded there
 POINTNET_PAD_Z = True
 
-
-def pointnet_graph(edge_index: torch.Tensor, n_src: int, n_dst: int, loops: bool = False) -> GraphIndex:
-    """The adjacency ``pointnet_pairs`` / ``pointnet_aggregate`` run on: ``graph_index(edge_index, max(n_src, n_dst),
-    self_loops=loops, normalize=False)``."""
-    return graph_index(edge_index, max(int(n_src), int(n_dst)), self_loops=bool(loops), normalize=False)
-
-
-def _pointnet_edge_rows(g: GraphIndex, loops: bool) -> int:
-    return g.num_input_edges + (g.num_nodes if loops else 0)
-
-
-def _pointnet_pair_fwd(g: GraphIndex, x, pos_src, pos_dst, loops: bool, pad: bool = False) -> torch.Tensor:
-    """z [E', F + 3] in the order of the edge rows: ``[x[src_q], pos_src[src_q] - pos_dst[dst_q]]``, a loop row
-    ``[x[i], 0, 0, 0]``; every row written once.  ``x`` None: F = 0.  ``pad``: a row stride rounded up to 4; the
-    result is then a view of the padded buffer, whose padding columns the kernel writes as zeros."""
-    from .neighbors import _ld
-    ns, nd = pos_src.size(0), pos_dst.size(0)
-    f = x.size(1) if x is not None else 0
-    rows = _pointnet_edge_rows(g, loops)
-    ldz = (f + 3 + 3) // 4 * 4 if pad else f + 3
-    z = torch.empty((rows, ldz), dtype=torch.float32, device=pos_src.device)
-    ei = g.edge_index
-    _lib.check(_lib.lib().dc_pointnet_pair_fwd(
-        ei[0].data_ptr(), ei[1].data_ptr(), _ptr(x), _rowmajor(x, "x") if x is not None else f, pos_src.data_ptr(),
-        _ld(pos_src), pos_dst.data_ptr(), _ld(pos_dst), z.data_ptr(), ldz, ns, nd, g.num_input_edges, f, int(loops),
-        ldz - (f + 3), current_stream_ptr(pos_src.device)), "dc_pointnet_pair_fwd")
-    return z[:, :f + 3] if pad else z
-
-
-def _pointnet_pair_bwd(g: GraphIndex, gz, ns: int, nd: int, loops: bool, want=(True, True, True)):
-    """-> (g_x [Ns, F], g_pos_src [Ns, 3], g_pos_dst [Nd, 3]), each None where ``want`` says so (and g_x for F = 0):
-    compensated sums over the sorted sets in their order."""
-    f, dev = gz.size(1) - 3, gz.device
-    gx = torch.empty((ns, f), dtype=torch.float32, device=dev) if want[0] and f > 0 else None
-    gps = torch.empty((ns, 3), dtype=torch.float32, device=dev) if want[1] else None
-    gpd = torch.empty((nd, 3), dtype=torch.float32, device=dev) if want[2] else None
-    _lib.check(_lib.lib().dc_pointnet_pair_bwd(
-        g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), g.fwd.perm.data_ptr(), g.bwd.ptr.data_ptr(),
-        g.bwd.other.data_ptr(), g.bwd.perm.data_ptr(), gz.data_ptr(), _rowmajor(gz, "gz"), _ptr(gx), max(f, 1),
-        _ptr(gps), 3, _ptr(gpd), 3, ns, nd, g.num_input_edges, f, int(loops), current_stream_ptr(dev)),
-        "dc_pointnet_pair_bwd")
-    return gx, gps, gpd
-
-
-def _pointnet_reduce_bwd(g: GraphIndex, m, y, cnt, gy, mode: int, loops: bool) -> torch.Tensor:
-    """g_m [E', C] in the order of the edge rows, every row written once (a removed input loop: zeros); ``m``, ``y``,
-    ``cnt``: the max only.  ``gy`` has the destinations' rows."""
-    nd, c = gy.shape
-    rows = _pointnet_edge_rows(g, loops)
-    gm = torch.empty((rows, c), dtype=torch.float32, device=gy.device)
-    ei = g.edge_index
-    saved = [m.data_ptr(), _rowmajor(m, "m"), y.data_ptr(), _rowmajor(y, "y"), cnt.data_ptr(),
-             _rowmajor(cnt, "cnt", (torch.int32,))] if mode == 2 else [None, c, None, c, None, c]
-    _lib.check(_lib.lib().dc_pointnet_reduce_bwd(
-        ei[0].data_ptr(), ei[1].data_ptr(), g.fwd.ptr.data_ptr(), *saved, gy.data_ptr(), _rowmajor(gy, "gy"),
-        gm.data_ptr(), c, mode, g.num_nodes, nd, g.num_input_edges, c, int(loops), current_stream_ptr(gy.device)),
-        "dc_pointnet_reduce_bwd")
-    return gm
-
-
-class _PointnetPairFn(torch.autograd.Function):
-    """``[x_j, pos_j - pos_i]`` per edge row: one launch forward, one backward; nothing is saved but the graph."""
-
-    @staticmethod
-    def forward(ctx, g: Optional[GraphIndex], x, pos_src, pos_dst, loops: bool, pad: bool):
-        ns, nd = pos_src.size(0), pos_dst.size(0)
-        f = x.size(1) if x is not None else 0
-        rows = _pointnet_edge_rows(g, loops) if g is not None else 0
-        ctx.g, ctx.loops, ctx.sizes = g, loops, (ns, nd, f)
-        ctx.empty = rows == 0 or ns == 0 or nd == 0              # no row, or every edge names a node that is not there
-        if ctx.empty:                        # nothing to launch (an empty tensor has no address)
-            return pos_src.new_zeros((rows, f + 3))
-        return _pointnet_pair_fwd(g, x, pos_src, pos_dst, loops, pad)
-
-    @staticmethod
-    def backward(ctx, gz):
-        ns, nd, f = ctx.sizes
-        want = (f > 0 and ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3])
-        if ctx.empty:
-            gx, gps, gpd = gz.new_zeros((ns, f)), gz.new_zeros((ns, 3)), gz.new_zeros((nd, 3))
-        else:
-            gx, gps, gpd = _pointnet_pair_bwd(ctx.g, _sage_grad(gz), ns, nd, ctx.loops, want)
-        return (None, gx if want[0] else None, gps if want[1] else None, gpd if want[2] else None, None, None)
-
-
-class _PointnetReduceFn(torch.autograd.Function):
-    """``sum`` / ``mean`` / ``max`` of edge rows per destination of a bipartite (or loops) set: one launch forward
-    (``dc_edge_reduce_fwd``), one backward (``dc_pointnet_reduce_bwd``).  The max saves m, y and cnt."""
-
-    @staticmethod
-    def forward(ctx, g: Optional[GraphIndex], m, mode: int, nd: int, loops: bool):
-        ctx.g, ctx.mode, ctx.loops, ctx.rows = g, mode, loops, m.size(0)
-        ctx.empty = nd == 0 or m.size(0) == 0
-        if ctx.empty:                        # no edge row: every destination is 0; no destination: no row
-            return m.new_zeros((nd, m.size(1)))
-        y, cnt = _edge_reduce_fwd(g, m, mode, nd)
-        if mode == 2:
-            ctx.save_for_backward(m, y, cnt)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        if ctx.empty:
-            return None, gy.new_zeros((ctx.rows, gy.size(1))), None, None, None
-        m, y, cnt = ctx.saved_tensors if ctx.mode == 2 else (None, None, None)
-        return None, _pointnet_reduce_bwd(ctx.g, m, y, cnt, _sage_grad(gy), ctx.mode, ctx.loops), None, None, None
-
-
-def _pointnet_graph_check(who: str, g: GraphIndex, loops: bool, t: torch.Tensor, what: str) -> None:
-    if g.self_loops != bool(loops) or g.normalize or g.edge_index is None or g.fwd.row_offset or g.bwd.row_offset:
-        raise ValueError(f"{who}: the graph must be built from one edge_index with self_loops={bool(loops)}, "
-                         "normalize=False (not a merged adjacency or a row window of one)")
-    if g.device != t.device:
-        raise RuntimeError(f"{who}: {what} is on {t.device} but the graph is on {g.device}")
-
-
-def pointnet_pairs(g: Optional[GraphIndex], x_src: Optional[torch.Tensor], pos_src: torch.Tensor,
-                   pos_dst: torch.Tensor, loops: bool = False, pad: Optional[bool] = None) -> torch.Tensor:
-    """``z [E', F + 3]`` with ``z[q] = [x_src[j], pos_src[j] - pos_dst[i]]`` for every edge ``q = (j -> i)`` of ``g``, rows
-    in the order of the ``edge_index`` the graph was built from - the per-edge input of PyG's ``PointNetConv``.
-    ``g``: ``pointnet_graph(edge_index, Ns, Nd, loops)``.  ``x_src``: float32 ``[Ns, F >= 1]`` with unit inner stride (a
-    column slice passes as it is) or None (``F = 0``: positions alone); ``pos_src`` ``[Ns, 3]``, ``pos_dst`` ``[Nd, 3]``:
-    float32 positions as ``neighbors`` takes them (a row stride is allowed).  An edge that names a source outside
-    ``[0, Ns)`` or a destination outside ``[0, Nd)`` gets a zero row.  ``loops``: one node set (``Ns == Nd == N``); ``E' =
-    E + N``, row ``E + i`` is ``[x_src[i], 0, 0, 0]``.  One autograd node: the backward is one launch
-    of compensated sums in the order of the sorted sets, for ``x_src``, ``pos_src`` and ``pos_dst`` - each only where it
-    wants a gradient; pass the same tensor as both positions and autograd adds the two.  The edge list must stay
-    unchanged until the backward has run.  No edge row, ``Ns = 0`` or ``Nd = 0``: zeros of the right shape, no launch.
-    ``pad``: ``z``'s row stride rounded up to 4 floats - ``z`` is then a non-contiguous view (unit inner stride) of a buffer
-    whose padding columns hold zeros; default: ``POINTNET_PAD_Z``'s rule, padded exactly where ``F % 4 == 0``."""
-    from .neighbors import _check_points
-    loops = bool(loops)
-    if x_src is not None:
-        x_src = resolve(x_src)
-        _require_cuda(x_src, "x_src")
-        if x_src.dim() != 2 or x_src.dtype != torch.float32 or x_src.size(1) == 0:
-            raise ValueError(f"pointnet_pairs: x_src must be a float32 [Ns, F >= 1] tensor or None, got "
-                             f"{tuple(x_src.shape)} {x_src.dtype}")
-    _check_points(pos_src, "pos_src")
-    _check_points(pos_dst, "pos_dst")
-    ns, nd = pos_src.size(0), pos_dst.size(0)
-    if x_src is not None and x_src.size(0) != ns:
-        raise ValueError(f"pointnet_pairs: x_src has {x_src.size(0)} rows but pos_src has {ns} points")
-    if pos_dst.device != pos_src.device or (x_src is not None and x_src.device != pos_src.device):
-        raise RuntimeError("pointnet_pairs: x_src, pos_src and pos_dst must be on one device")
-    if loops and ns != nd:
-        raise ValueError(f"pointnet_pairs: loops need one node set (Ns={ns}, Nd={nd})")
-    f = x_src.size(1) if x_src is not None else 0
-    pad = (POINTNET_PAD_Z and f > 0 and f % 4 == 0) if pad is None else bool(pad)
-    if g is None:
-        if max(ns, nd) != 0:
-            raise ValueError("pointnet_pairs: g may be None only without any node")
-        return _PointnetPairFn.apply(None, x_src, pos_src, pos_dst, loops, pad)
-    _pointnet_graph_check("pointnet_pairs", g, loops, pos_src, "pos_src")
-    if g.num_nodes != max(ns, nd):
-        raise ValueError(f"pointnet_pairs: the graph has {g.num_nodes} rows but max(Ns, Nd) = {max(ns, nd)}")
-    return _PointnetPairFn.apply(g, None if x_src is None else _edge_rows(x_src), pos_src, pos_dst, loops, pad)
-
-
-def pointnet_aggregate(g: Optional[GraphIndex], m: torch.Tensor, reduce: str = "max", num_dst: Optional[int] = None,
-                       loops: bool = False) -> torch.Tensor:
-    """``reduce`` (``"sum"`` / ``"mean"`` / ``"max"``) per destination ``i < num_dst`` of the rows ``m[q]`` that live on the
-    edge rows of ``g`` -> ``[num_dst, C]`` - ``edge_aggregate`` for a bipartite set (``g = pointnet_graph(...)``, only
-    ``num_dst`` rows are reduced; default: all rows of ``g``) and for ``loops`` (``m`` has ``E + N`` rows, an input edge
-    with ``src == dst`` is ignored, the mean's degree counts the loop).  Sums, the max's even split and the layouts as
-    ``edge_aggregate``.  One autograd node; the backward writes every row of the gradient
-    once - zeros for an ignored row - and reads the endpoints from ``g.edge_index``."""
-    if not isinstance(reduce, str) or reduce not in EDGE_REDUCE_MODES:
-        raise ValueError(f"pointnet_aggregate: reduce must be 'sum', 'mean' or 'max', got {reduce!r}")
-    m = resolve(m)
-    _require_cuda(m, "m")
-    if m.dim() != 2 or m.dtype != torch.float32 or m.size(1) == 0:
-        raise ValueError(f"pointnet_aggregate: m must be a float32 [E', C >= 1] tensor, got {tuple(m.shape)} {m.dtype}")
-    mode, loops = EDGE_REDUCE_MODES[reduce], bool(loops)
-    if g is None:
-        if m.size(0) != 0 or (num_dst or 0) != 0:
-            raise ValueError("pointnet_aggregate: g may be None only for an m without rows and no destination")
-        return _PointnetReduceFn.apply(None, m, mode, 0, loops)
-    _pointnet_graph_check("pointnet_aggregate", g, loops, m, "m")
-    nd = g.num_nodes if num_dst is None else int(num_dst)
-    if not 0 <= nd <= g.num_nodes or (loops and nd != g.num_nodes):
-        raise ValueError(f"pointnet_aggregate: num_dst = {nd} does not fit the graph's {g.num_nodes} rows"
-                         f"{' (loops need all of them)' if loops else ''}")
-    rows = _pointnet_edge_rows(g, loops)
-    if rows != m.size(0):
-        raise ValueError(f"pointnet_aggregate: m has {m.size(0)} rows but the graph has {rows} edge rows")
-    return _PointnetReduceFn.apply(g, _edge_rows(m), mode, nd, loops)
-
-
-# --------------------------------------------------------------------------- #
-# ChebConv (dc_cheb.hip): the Chebyshev basis [Tx_0 | ... | Tx_{K-1}] of the scaled Laplacian as ONE autograd node.
-# Every recurrence step - the hop, the diagonal term, the doubling and the "- Tx_{k-2}" - is one launch; the backward
-# is the adjoint recurrence over the by-source set, K - 1 launches on a private copy of the slab's gradient.
-# --------------------------------------------------------------------------- #
-CHEB_MODES = {"sym": 0, "rw": 1}
-
-
-def cheb_diagonal(lam: float) -> float:
-    """``b = 2 / lambda_max - 1``: the diagonal term of the scaled Laplacian, the same for every node."""
-    return 2.0 / lam - 1.0
-
-
-def _cheb_norm(g: GraphIndex, mode: int, lam: float):
-    """-> (wl_fwd, wl_bwd): ``(2 * -w) / lam`` per slot of the by-destination and of the by-source set, 0 for a self
-    loop; ``w`` from the out-degrees over the non-loop edges (``dc_cheb_norm``: two launches)."""
-    dev, cap, n = g.device, max(g.capacity, 1), max(g.num_nodes, 1)
-    wl_fwd, wl_bwd, dinv = torch.empty(2 * cap + n, dtype=torch.float32, device=dev).split((cap, cap, n))
-    _lib.check(_lib.lib().dc_cheb_norm(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), g.bwd.ptr.data_ptr(),
-                                       g.bwd.other.data_ptr(), mode, lam, dinv.data_ptr(), wl_fwd.data_ptr(),
-                                       wl_bwd.data_ptr(), g.num_nodes, current_stream_ptr(dev)), "dc_cheb_norm")
-    return wl_fwd, wl_bwd
-
-
-def _cheb_hop(adj: SortedAdjacency, wl: torch.Tensor, x: torch.Tensor, y: torch.Tensor, b: float, k: int, c: int,
-              z: Optional[torch.Tensor] = None, z2: Optional[torch.Tensor] = None,
-              y2: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """One recurrence step (``dc_cheb_hop``): ``y = k (sum_p wl[p] x[other[p]] + b x) + c z`` and, with ``y2``,
-    ``y2 = z2 - x``.  Every operand a row-major (possibly column-sliced) ``[N, F]`` view; ``y`` may be ``z`` and ``y2``
-    may be ``z2``, neither may be ``x``."""
-    n, f = x.shape
-    for name, t in (("y", y), ("z", z), ("z2", z2), ("y2", y2)):
-        if t is not None and t.shape != x.shape:
-            raise ValueError(f"cheb hop: {name} shape mismatch")
-    if (c != 0) != (z is not None) or (y2 is None) != (z2 is None):
-        raise ValueError("cheb hop: z goes with c != 0, z2 with y2")
-    if adj.ptr.numel() != n + 1:
-        raise ValueError(f"cheb hop: x has {n} rows but the graph has {adj.ptr.numel() - 1} nodes")
-
-    def ld(t, what):
-        return _rowmajor(t, what) if t is not None else 0
-    _lib.check(_lib.lib().dc_cheb_hop(adj.ptr.data_ptr(), adj.other.data_ptr(), wl.data_ptr(), x.data_ptr(), ld(x, "x"),
-                                      _ptr(z), ld(z, "z"), y.data_ptr(), ld(y, "y"), _ptr(z2), ld(z2, "z2"), _ptr(y2),
-                                      ld(y2, "y2"), b, k, c, n, f, current_stream_ptr(x.device)), "dc_cheb_hop")
-    return y
-
-
-class _ChebBasisFn(torch.autograd.Function):
-    """``[Tx_0 | ... | Tx_{K-1}]``: a copy of x and K - 1 step launches forward; backward K - 1 launches of the adjoint
-    recurrence.  Saved: the two weight arrays (recomputed on every forward: a rebuilt adjacency is followed), nothing
-    of the features - the recurrence is linear."""
-
-    @staticmethod
-    def forward(ctx, g: Optional[GraphIndex], x, k: int, mode: int, lam: float):
-        n, f = x.shape
-        ctx.g, ctx.k, ctx.b, ctx.f = g, k, cheb_diagonal(lam), f
-        slab = torch.empty((n, k * f), dtype=torch.float32, device=x.device)
-        if n == 0:
-            return slab                          # no rows: nothing to launch (an empty tensor has no address)
-        slab[:, :f] = x
-        if k == 1:
-            return slab
-        wl_fwd, ctx.wl_bwd = _cheb_norm(g, mode, lam)
-        blk = [slab[:, i * f:(i + 1) * f] for i in range(k)]
-        _cheb_hop(g.fwd, wl_fwd, blk[0], blk[1], ctx.b, 1, 0)
-        for i in range(2, k):
-            _cheb_hop(g.fwd, wl_fwd, blk[i - 1], blk[i], ctx.b, 2, -1, z=blk[i - 2])
-        return slab
-
-    @staticmethod
-    def backward(ctx, gslab):
-        k, f = ctx.k, ctx.f
-        if gslab.size(0) == 0:
-            return None, gslab.new_zeros((0, f)), None, None, None
-        if k == 1:
-            return None, _grad_layout(gslab, 0), None, None, None
-        # a private copy: the steps below update it in place, and the gradient autograd handed in is not ours to write
-        grad = _grad_layout(gslab, 0)
-        if grad.data_ptr() == gslab.data_ptr():
-            grad = grad.clone()
-        blk = [grad[:, i * f:(i + 1) * f] for i in range(k)]
-        g, wl = ctx.g, ctx.wl_bwd
-        for i in range(k - 1, 1, -1):            # G_{i-1} += 2 L^T G_i  and  G_{i-2} -= G_i, one launch
-            _cheb_hop(g.bwd, wl, blk[i], blk[i - 1], ctx.b, 2, 1, z=blk[i - 1], z2=blk[i - 2], y2=blk[i - 2])
-        _cheb_hop(g.bwd, wl, blk[1], blk[0], ctx.b, 1, 1, z=blk[0])          # G_0 += L^T G_1
-        return None, blk[0], None, None, None
-
-
-def cheb_lambda(lambda_max, what: str = "cheb_basis") -> float:
-    """``lambda_max`` as the Python float the kernels take: None -> 2.0; a tensor or a value <= 0 raises."""
-    if lambda_max is None:
-        return 2.0
-    if isinstance(lambda_max, torch.Tensor):
-        raise NotImplementedError(f"{what}: a tensor lambda_max (per-graph values included) is not supported; pass a "
-                                  "Python number")
-    if isinstance(lambda_max, bool) or not isinstance(lambda_max, (int, float)):
-        raise TypeError(f"{what}: lambda_max must be None or a Python number, got {type(lambda_max).__name__}")
-    if not lambda_max > 0:
-        raise ValueError(f"{what}: lambda_max must be > 0, got {lambda_max}")
-    return float(lambda_max)
-
-
-def cheb_basis(g: Optional[GraphIndex], x: torch.Tensor, K: int, normalization: str = "sym",
-               lambda_max=None) -> torch.Tensor:
-    """The Chebyshev basis ``[Tx_0 | Tx_1 | ... | Tx_{K-1}]`` ``[N, K*F]`` of PyG's ``ChebConv``: ``Tx_0 = x``,
-    ``Tx_1 = L^ x``, ``Tx_k = 2 L^ Tx_{k-1} - Tx_{k-2}`` with ``L^ x_i = sum_{j->i} wl x_j + (2 / lambda_max - 1) x_i``,
-    ``wl = (2 * -w) / lambda_max`` and ``w`` the ``normalization`` (``"sym"``: ``deg_j^-1/2 deg_i^-1/2``, ``"rw"``:
-    ``1 / deg_j``) by OUT-degree over the edges of ``g`` without its self loops - a ``GraphIndex`` built with
-    ``self_loops=False, normalize=False``; self loops in it are dropped here, duplicates count.  ``lambda_max``: None
-    (2.0) or a Python number > 0.  ``x``: float32 ``[N, F >= 1]`` on the graph's device.  One autograd node,
-    differentiable in ``x``.  ``K = 1`` and ``N = 0`` need no graph (``g`` may be None) and launch no hop."""
-    if not isinstance(K, int) or isinstance(K, bool) or K < 1:
-        raise ValueError(f"cheb_basis: K must be an int >= 1, got {K!r}")
-    if normalization not in CHEB_MODES:
-        raise ValueError(f"cheb_basis: normalization must be 'sym' or 'rw', got {normalization!r}")
-    lam = cheb_lambda(lambda_max)
-    x = resolve(x)
-    _require_cuda(x, "x")
-    if x.dim() != 2 or x.dtype != torch.float32 or x.size(1) == 0:
-        raise ValueError(f"cheb_basis: x must be a float32 [N, F >= 1] tensor, got {tuple(x.shape)} {x.dtype}")
-    if x.size(0) and K > 1:
-        if g is None:
-            raise ValueError("cheb_basis: g may be None only for K = 1 or an x without rows")
-        if g.self_loops or g.normalize or g.fwd.row_offset or g.bwd.row_offset:
-            raise ValueError("cheb_basis: the graph must be built with self_loops=False, normalize=False (and be no row "
-                             "window of a merged adjacency)")
-        if g.device != x.device:
-            raise RuntimeError(f"cheb_basis: x is on {x.device} but the graph is on {g.device}")
-        if g.num_nodes != x.size(0):
-            raise ValueError(f"cheb_basis: x has {x.size(0)} rows but the graph has {g.num_nodes} nodes")
-    return _ChebBasisFn.apply(g, x, K, CHEB_MODES[normalization], lam)
-
-
-# --------------------------------------------------------------------------- #
-# GMMConv (dc_gmm.hip): per in-edge a mixture of K Gaussians over the edge's D pseudo-coordinates weights the K column
-# blocks of the source row of h = x @ g.  The weights w [E, K] are formed once, in the order of the input edges (read
-# through the adjacency's ``perm``), and saved for the backward.  One launcher per C entry.
-# --------------------------------------------------------------------------- #
-GMM_MAX_K = 64        # DC_GMM_MAX_K in include/deformcontact.h
-GMM_MAX_D = 16        # DC_GMM_MAX_D
-GMM_REDUCES = ("mean", "add")
-
-
-def gmm_relu_ok(m: int) -> bool:
-    """Output widths at which ``gmm_aggregate(relu=True)`` runs: those of the mask pass of its backward
-    (``dc_mask_colsum_f32``: a multiple of 4 that divides 1024).  At any other width the ReLU goes behind the call."""
-    return m % 4 == 0 and 4 <= m <= 1024 and 256 % (m // 4) == 0
-
-
-def _gmm_weights(a, mu, sigma) -> torch.Tensor:
-    """w [E, K]: ``exp(sum_d -0.5 (a[q,d] - mu[k,d])^2 / (1e-15 + sigma[k,d]^2))`` in the order of the input edges."""
-    ne, (k, d) = a.size(0), mu.shape
-    w = torch.empty((ne, k), dtype=torch.float32, device=a.device)
-    if ne == 0:
-        return w
-    _lib.check(_lib.lib().dc_gmm_weights(a.data_ptr(), _rowmajor(a, "edge_attr"), mu.data_ptr(), sigma.data_ptr(),
-                                         w.data_ptr(), ne, k, d, current_stream_ptr(a.device)), "dc_gmm_weights")
-    return w
-
-
-def _gmm_fwd(g: GraphIndex, w, h, m: int, mean: bool, base=None, relu: bool = False) -> torch.Tensor:
-    """y [N, M]: ``sum_p sum_k w[perm[p], k] h[other[p], k*M:(k+1)*M]`` in p, then k order; ``mean``: divided by the
-    in-degree; ``+ base``; ``relu``: ``max(., 0)``."""
-    n, k = h.size(0), w.size(1)
-    y = torch.empty((n, m), dtype=torch.float32, device=h.device)
-    _lib.check(_lib.lib().dc_gmm_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), g.fwd.perm.data_ptr(),
-                                     w.data_ptr() if w.size(0) else None, h.data_ptr(), _rowmajor(h, "h"), _ptr(base),
-                                     _rowmajor(base, "base") if base is not None else 0, int(mean), int(relu),
-                                     y.data_ptr(), m, n, w.size(0), k, m, current_stream_ptr(h.device)), "dc_gmm_fwd")
-    return y
-
-
-def _gmm_bwd_h(g: GraphIndex, w, gy, mean: bool) -> torch.Tensor:
-    """g_h [N, K*M] over the transposed set: ``sum_t w[perm_t[t], k] gs[other_t[t], c]``, ``gs = g_y / deg`` (mean, the
-    in-degree read from the forward ``ptr``) or ``g_y``."""
-    (n, m), k = gy.shape, w.size(1)
-    gh = torch.empty((n, k * m), dtype=torch.float32, device=gy.device)
-    _lib.check(_lib.lib().dc_gmm_bwd_h(g.bwd.ptr.data_ptr(), g.bwd.other.data_ptr(), g.bwd.perm.data_ptr(),
-                                       g.fwd.ptr.data_ptr() if mean else None, w.data_ptr() if w.size(0) else None,
-                                       gy.data_ptr(), _rowmajor(gy, "gy"), gh.data_ptr(), k * m, n, w.size(0), k, m,
-                                       current_stream_ptr(gy.device)), "dc_gmm_bwd_h")
-    return gh
-
-
-def _gmm_bwd_w(g: GraphIndex, h, gy, k: int, mean: bool) -> torch.Tensor:
-    """g_w [E, K] in the order of the input edges: ``sum_c gs[dst_q, c] h[src_q, k*M + c]``."""
-    n, m = gy.shape
-    ne = g.num_input_edges
-    gw = torch.empty((ne, k), dtype=torch.float32, device=gy.device)
-    if ne == 0:
-        return gw
-    ei = g.edge_index
-    _lib.check(_lib.lib().dc_gmm_bwd_w(ei[0].data_ptr(), ei[1].data_ptr(), g.fwd.ptr.data_ptr() if mean else None,
-                                       h.data_ptr(), _rowmajor(h, "h"), gy.data_ptr(), _rowmajor(gy, "gy"),
-                                       gw.data_ptr(), n, ne, k, m, current_stream_ptr(gy.device)), "dc_gmm_bwd_w")
-    return gw
-
-
-def _gmm_bwd_params(gw, w, a, mu, sigma, want_a: bool):
-    """-> (g_mu [K, D], g_sigma [K, D], g_a [E, D] or None) from ``t = g_w w`` and ``r = (a - mu) / (1e-15 +
-    sigma^2)``: ``sum_q t r``, ``(sum_q t r r) sigma``, ``-sum_k t r``."""
-    ne, (k, d), dev = a.size(0), mu.shape, a.device
-    ga = torch.empty((ne, d), dtype=torch.float32, device=dev) if want_a else None
-    if ne == 0:
-        return torch.zeros_like(mu), torch.zeros_like(sigma), ga
-    gmu, gsigma = torch.empty((2, k, d), dtype=torch.float32, device=dev).unbind(0)
-    L = _lib.lib()
-    ws = torch.empty(max(L.dc_gmm_params_workspace_bytes(ne, k, d), 16), dtype=torch.uint8, device=dev)
-    _lib.check(L.dc_gmm_bwd_params(gw.data_ptr(), w.data_ptr(), a.data_ptr(), _rowmajor(a, "edge_attr"), mu.data_ptr(),
-                                   sigma.data_ptr(), ws.data_ptr(), ws.numel(), gmu.data_ptr(), gsigma.data_ptr(),
-                                   _ptr(ga), d, ne, k, d, current_stream_ptr(dev)), "dc_gmm_bwd_params")
-    return gmu, gsigma, ga
-
-
-class _GmmAggFn(torch.autograd.Function):
-    """The Gaussian-mixture aggregation: two launches forward (the weights, the K-way gather); backward the ReLU mask
-    (``relu``), one launch for g_h, one for g_w and two for g_mu / g_sigma (three with g_a) - the last three skipped when
-    neither ``edge_attr`` nor ``mu`` nor ``sigma`` needs a gradient.  Saved: h, edge_attr, mu, sigma, the weights
-    w [E, K] and, with ``relu``, the output."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, a, mu, sigma, base, m: int, mean: bool, relu: bool):
-        ctx.g, ctx.m, ctx.mean, ctx.relu, ctx.empty = g, m, mean, relu, h.size(0) == 0
-        if ctx.empty:                        # no rows: nothing to launch (an empty tensor has no address)
-            ctx.shapes = (h.shape, a.shape, mu.shape)
-            return h.new_empty((0, m))
-        w = _gmm_weights(a, mu, sigma)
-        y = _gmm_fwd(g, w, h, m, mean, base, relu)
-        ctx.save_for_backward(h, a, mu, sigma, w, y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        need = ctx.needs_input_grad
-        if ctx.empty:
-            hs, as_, ps = ctx.shapes
-            return (None, gy.new_zeros(hs) if need[1] else None, gy.new_zeros(as_) if need[2] else None,
-                    gy.new_zeros(ps) if need[3] else None, gy.new_zeros(ps) if need[4] else None,
-                    gy.new_zeros(gy.shape) if need[5] else None, None, None, None)
-        h, a, mu, sigma, w, y = ctx.saved_tensors
-        if ctx.relu:
-            gy, _ = _mask_and_bias_grad(_grad_layout(gy, 0), y, None, False)
-        else:
-            gy = _sage_grad(gy)
-        gh = _gmm_bwd_h(ctx.g, w, gy, ctx.mean) if need[1] else None
-        ga = gmu = gsigma = None
-        if need[2] or need[3] or need[4]:
-            gw = _gmm_bwd_w(ctx.g, h, gy, w.size(1), ctx.mean)
-            gmu, gsigma, ga = _gmm_bwd_params(gw, w, a, mu, sigma, need[2])
-        return (None, gh, ga, gmu if need[3] else None, gsigma if need[4] else None, gy if need[5] else None, None,
-                None, None)
-
-
-def gmm_aggregate(g: Optional[GraphIndex], h: torch.Tensor, edge_attr: torch.Tensor, mu: torch.Tensor,
-                  sigma: torch.Tensor, reduce: str = "mean", base: Optional[torch.Tensor] = None,
-                  relu: bool = False) -> torch.Tensor:
-    """PyG ``GMMConv``'s aggregation (``separate_gaussians=False``): ``s_i = sum_{j->i} sum_k w_k(e_ji) h[j, k*M:(k+1)*M]``
-    with ``w_k(e) = exp(sum_d -0.5 (e_d - mu[k,d])^2 / (1e-15 + sigma[k,d]^2))`` over the edges of ``g`` - a
-    ``GraphIndex`` of one ``edge_index`` built with ``self_loops=False, normalize=False``: the edge set as given,
-    duplicates counting.  ``reduce="mean"`` divides by the in-degree (duplicates counted; a row without edges is 0),
-    ``"add"`` does not; then ``+ base`` (``[N, M]``, the root term with its bias; None: none) and, with ``relu``, the
-    ReLU - all in the gather's epilogue.  ``h``: float32 ``[N, K*M]``, column ``k*M + c`` kernel k, channel c;
-    ``edge_attr``: float32 ``[E, D]`` with rows in the order of that ``edge_index``; ``mu``, ``sigma``: float32 ``[K, D]``,
-    ``1 <= K <= 64``, ``1 <= D <= 16``, read BY THE KERNELS (parameters changed in place between two replays of a
-    captured step are followed).  All on the graph's device; ``h``, ``edge_attr`` and ``base`` with unit inner stride
-    (column slices pass as they are).  One autograd node, differentiable in ``h``, ``edge_attr`` (skipped when it needs
-    no gradient), ``mu``, ``sigma`` and ``base``; with ``relu`` the backward masks by ``y > 0``: ``relu'(0) = 0``, and
-    ``M`` must be a width of the mask pass (``gmm_relu_ok``).  The gradient of ``edge_attr``, ``mu`` and ``sigma`` reads
-    the endpoints from ``g.edge_index`` at backward time while the forward read the sorted set built from it: the edge
-    list must stay unchanged until the backward has run.  ``N = 0`` returns an empty tensor
-    without a launch (``g`` may then be None)."""
-    if not isinstance(reduce, str) or reduce not in GMM_REDUCES:
-        raise ValueError(f"gmm_aggregate: reduce must be 'mean' or 'add', got {reduce!r}")
-    h, edge_attr = resolve(h), resolve(edge_attr)
-    for name, t in (("h", h), ("edge_attr", edge_attr), ("mu", mu), ("sigma", sigma)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"gmm_aggregate: {name} must be a tensor, got {type(t).__name__}")
-    if mu.dim() != 2 or mu.dtype != torch.float32 or sigma.shape != mu.shape or sigma.dtype != torch.float32:
-        raise ValueError(f"gmm_aggregate: mu and sigma must be float32 [K, D] tensors of one shape, got "
-                         f"{tuple(mu.shape)} {mu.dtype} and {tuple(sigma.shape)} {sigma.dtype}")
-    k, d = mu.shape
-    if not 1 <= k <= GMM_MAX_K:
-        raise ValueError(f"gmm_aggregate: kernel_size K must be within 1..{GMM_MAX_K}, got {k}")
-    if not 1 <= d <= GMM_MAX_D:
-        raise ValueError(f"gmm_aggregate: dim D must be within 1..{GMM_MAX_D}, got {d}")
-    if h.dim() != 2 or h.dtype != torch.float32 or h.size(1) == 0 or h.size(1) % k:
-        raise ValueError(f"gmm_aggregate: h must be a float32 [N, K*M] tensor with K = {k}, M >= 1, got "
-                         f"{tuple(h.shape)} {h.dtype}")
-    m = h.size(1) // k
-    if edge_attr.dim() != 2 or edge_attr.dtype != torch.float32 or edge_attr.size(1) != d:
-        raise ValueError(f"gmm_aggregate: edge_attr must be a float32 [E, {d}] tensor, got {tuple(edge_attr.shape)} "
-                         f"{edge_attr.dtype}")
-    if base is not None:
-        base = resolve(base)
-        if not isinstance(base, torch.Tensor) or base.dim() != 2 or base.dtype != torch.float32 or \
-                base.shape != (h.size(0), m):
-            raise ValueError(f"gmm_aggregate: base must be a float32 [{h.size(0)}, {m}] tensor (or None)")
-    if relu and not gmm_relu_ok(m):
-        raise ValueError(f"gmm_aggregate: relu=True needs M to be a multiple of 4 that divides 1024, got {m}; apply "
-                         "the ReLU behind the call")
-    _require_cuda(h, "h")
-    for name, t in (("edge_attr", edge_attr), ("mu", mu), ("sigma", sigma), ("base", base)):
-        if t is not None:
-            _require_cuda(t, name)
-            if t.device != h.device:
-                raise RuntimeError(f"gmm_aggregate: h is on {h.device} but {name} is on {t.device}")
-    mean = reduce == "mean"
-    mu, sigma = mu.contiguous(), sigma.contiguous()
-    if h.size(0) == 0:
-        if edge_attr.size(0) != 0:
-            raise ValueError(f"gmm_aggregate: edge_attr has {edge_attr.size(0)} rows but h has no node")
-        return _GmmAggFn.apply(None, h, edge_attr, mu, sigma, base, m, mean, bool(relu))
-    if g is None:
-        raise ValueError("gmm_aggregate: g may be None only for an h without rows")
-    if g.self_loops or g.normalize or g.edge_index is None or g.fwd.row_offset or g.bwd.row_offset:
-        raise ValueError("gmm_aggregate: the graph must be built from one edge_index with self_loops=False, "
-                         "normalize=False (not a merged adjacency or a row window of one)")
-    if g.device != h.device:
-        raise RuntimeError(f"gmm_aggregate: h is on {h.device} but the graph is on {g.device}")
-    if g.num_nodes != h.size(0):
-        raise ValueError(f"gmm_aggregate: h has {h.size(0)} rows but the graph has {g.num_nodes} nodes")
-    if g.num_input_edges != edge_attr.size(0):
-        raise ValueError(f"gmm_aggregate: edge_attr has {edge_attr.size(0)} rows but the graph has "
-                         f"{g.num_input_edges} edges")
-
-    def rows(t):
-        # unit inner stride and rows that do not overlap (an expanded operand is copied); a column slice passes as it is
-        return t.contiguous() if (t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)) else t
-    return _GmmAggFn.apply(g, rows(h), rows(edge_attr), mu, sigma, rows(base) if base is not None else None, m, mean,
-                           bool(relu))
-
-
-# --------------------------------------------------------------------------- #
-# SplineConv (dc_spline.hip): per in-edge a B-spline of degree 1..3 over the edge's D pseudo-coordinates names S =
-# (degree+1)^D of the K column blocks of the source row of h = x @ weight[k] and weights them.  The basis values
-# b [E, S] and the block indices wi [E, S] are formed once, in the order of the input edges (read through the
-# adjacency's ``perm``), and saved for the backward.  ``kernel_size``, ``is_open_spline`` and ``degree`` are host values
-# copied into the kernel arguments.  One launcher per C entry.
-# --------------------------------------------------------------------------- #
-SPLINE_MAX_D = 4       # DC_SPLINE_MAX_D in include/deformcontact.h
-SPLINE_MAX_S = 64      # DC_SPLINE_MAX_S
-SPLINE_MAX_K = 1024    # DC_SPLINE_MAX_K
-SPLINE_REDUCES = ("mean", "add")
-
-
-def spline_geometry(kernel_size, is_open_spline, degree, dim: Optional[int] = None, who: str = "spline_aggregate"):
-    """``(ks, open, degree, K, S)`` as host ints - ``ks`` / ``open``: tuples of ``D`` ints - from an int or a sequence
-    of ``D`` ints, a bool or a sequence of ``D`` bools, and the degree; every cap of the layer checked (``ValueError``).
-    ``dim``: D where it is not given by a sequence."""
-    def seq(v, scalar, name):
-        if isinstance(v, torch.Tensor):
-            v = v.tolist()
-        if isinstance(v, scalar) and not (scalar is int and isinstance(v, bool)):
-            if dim is None:
-                raise ValueError(f"{who}: {name} must be a sequence of D values where dim is not given")
-            return [v] * dim
-        if not isinstance(v, (list, tuple)) or not all(isinstance(t, scalar) for t in v):
-            raise ValueError(f"{who}: {name} must be {'an int' if scalar is int else 'a bool'} or a sequence of them, "
-                             f"got {v!r}")
-        return list(v)
-    if isinstance(degree, bool) or not isinstance(degree, int) or degree not in (1, 2, 3):
-        raise ValueError(f"{who}: degree must be 1, 2 or 3, got {degree!r}")
-    if dim is not None and (isinstance(dim, bool) or not isinstance(dim, int) or not 1 <= dim <= SPLINE_MAX_D):
-        raise ValueError(f"{who}: dim must be an int within 1..{SPLINE_MAX_D}, got {dim!r}")
-    ks, op = seq(kernel_size, int, "kernel_size"), seq(is_open_spline, (bool, int), "is_open_spline")
-    d = dim if dim is not None else len(ks)
-    if not 1 <= d <= SPLINE_MAX_D:
-        raise ValueError(f"{who}: dim must be within 1..{SPLINE_MAX_D}, got {d}")
-    if len(ks) != d or len(op) != d:
-        raise ValueError(f"{who}: kernel_size and is_open_spline must have dim = {d} entries, got {len(ks)} and "
-                         f"{len(op)}")
-    s = (degree + 1) ** d
-    if s > SPLINE_MAX_S:
-        raise ValueError(f"{who}: (degree+1)^dim = {s} slots per edge, at most {SPLINE_MAX_S} are supported")
-    if any(isinstance(t, bool) or t < 1 for t in ks):
-        raise ValueError(f"{who}: every kernel_size must be an int >= 1, got {ks}")
-    k = math.prod(ks)
-    if k > SPLINE_MAX_K:
-        raise ValueError(f"{who}: the product of kernel_size is {k}, at most {SPLINE_MAX_K} is supported")
-    return tuple(ks), tuple(int(bool(t)) for t in op), degree, k, s
-
-
-def _spline_host(ks, op):
-    return _i64_array(list(ks)), (ctypes.c_int32 * len(op))(*op)
-
-
-def _spline_basis(a, ks, op, degree: int):
-    """-> (b [E, S] float32, wi [E, S] int32) in the order of the input edges: the basis products and the indices of
-    the weight matrices they belong to."""
-    ne, d = a.shape
-    s = (degree + 1) ** d
-    b = torch.empty((ne, s), dtype=torch.float32, device=a.device)
-    wi = torch.empty((ne, s), dtype=torch.int32, device=a.device)
-    if ne == 0:
-        return b, wi
-    hks, hop = _spline_host(ks, op)
-    _lib.check(_lib.lib().dc_spline_basis(a.data_ptr(), _rowmajor(a, "edge_attr"), hks, hop, degree, b.data_ptr(),
-                                          wi.data_ptr(), ne, d, current_stream_ptr(a.device)), "dc_spline_basis")
-    return b, wi
-
-
-def _spline_fwd(g: GraphIndex, b, wi, h, k: int, m: int, mean: bool, base=None, relu: bool = False) -> torch.Tensor:
-    """y [N, M]: ``sum_p (sum_s b[perm[p], s] h[other[p], wi[perm[p], s]*M:+M])`` - per edge the message over s in order,
-    the messages in p order; ``mean``: divided by the in-degree; ``+ base``; ``relu``: ``max(., 0)``."""
-    n, (ne, s) = h.size(0), b.shape
-    y = torch.empty((n, m), dtype=torch.float32, device=h.device)
-    _lib.check(_lib.lib().dc_spline_fwd(g.fwd.ptr.data_ptr(), g.fwd.other.data_ptr(), g.fwd.perm.data_ptr(),
-                                        b.data_ptr() if ne else None, wi.data_ptr() if ne else None, h.data_ptr(),
-                                        _rowmajor(h, "h"), _ptr(base), _rowmajor(base, "base") if base is not None else 0,
-                                        int(mean), int(relu), y.data_ptr(), m, n, ne, s, k, m,
-                                        current_stream_ptr(h.device)), "dc_spline_fwd")
-    return y
-
-
-def _spline_bwd_h(g: GraphIndex, b, wi, gy, k: int, mean: bool) -> torch.Tensor:
-    """g_h [N, K*M] over the transposed set: ``sum_t sum_{s: wi[perm_t[t], s] == k} b[perm_t[t], s] gs[other_t[t], c]``,
-    ``gs = g_y / deg`` (mean, the in-degree read from the forward ``ptr``) or ``g_y``; every column is written."""
-    (n, m), (ne, s) = gy.shape, b.shape
-    gh = torch.empty((n, k * m), dtype=torch.float32, device=gy.device)
-    _lib.check(_lib.lib().dc_spline_bwd_h(g.bwd.ptr.data_ptr(), g.bwd.other.data_ptr(), g.bwd.perm.data_ptr(),
-                                          g.fwd.ptr.data_ptr() if mean else None, b.data_ptr() if ne else None,
-                                          wi.data_ptr() if ne else None, gy.data_ptr(), _rowmajor(gy, "gy"),
-                                          gh.data_ptr(), k * m, n, ne, s, k, m, current_stream_ptr(gy.device)),
-               "dc_spline_bwd_h")
-    return gh
-
-
-def _spline_bwd_b(g: GraphIndex, wi, h, gy, k: int, mean: bool) -> torch.Tensor:
-    """g_b [E, S] in the order of the input edges: ``sum_c gs[dst_q, c] h[src_q, wi[q, s]*M + c]``."""
-    (n, m), (ne, s) = gy.shape, wi.shape
-    gb = torch.empty((ne, s), dtype=torch.float32, device=gy.device)
-    if ne == 0:
-        return gb
-    ei = g.edge_index
-    _lib.check(_lib.lib().dc_spline_bwd_b(ei[0].data_ptr(), ei[1].data_ptr(), g.fwd.ptr.data_ptr() if mean else None,
-                                          wi.data_ptr(), h.data_ptr(), _rowmajor(h, "h"), gy.data_ptr(),
-                                          _rowmajor(gy, "gy"), gb.data_ptr(), n, ne, s, k, m,
-                                          current_stream_ptr(gy.device)), "dc_spline_bwd_b")
-    return gb
-
-
-def _spline_bwd_a(gb, a, ks, op, degree: int) -> torch.Tensor:
-    """g_a [E, D]: ``float(ks[d] - degree open[d]) sum_s g_b[q, s] B'(f_d) prod_{d' != d} B(f_d')``."""
-    ne, d = a.shape
-    ga = torch.empty((ne, d), dtype=torch.float32, device=a.device)
-    if ne == 0:
-        return ga
-    hks, hop = _spline_host(ks, op)
-    _lib.check(_lib.lib().dc_spline_bwd_a(gb.data_ptr(), a.data_ptr(), _rowmajor(a, "edge_attr"), hks, hop, degree,
-                                          ga.data_ptr(), d, ne, d, current_stream_ptr(a.device)), "dc_spline_bwd_a")
-    return ga
-
-
-class _SplineAggFn(torch.autograd.Function):
-    """The B-spline aggregation: two launches forward (the basis, the S-way gather); backward the ReLU mask (``relu``),
-    one launch for g_h and - only when ``edge_attr`` needs a gradient - one for g_b and one for g_a.  Saved: h, the
-    basis b and the indices wi [E, S], ``edge_attr`` when its gradient is wanted and, with ``relu``, the output."""
-
-    @staticmethod
-    def forward(ctx, g: GraphIndex, h, a, base, geom, m: int, mean: bool, relu: bool):
-        ctx.g, ctx.geom, ctx.m, ctx.mean, ctx.relu, ctx.empty = g, geom, m, mean, relu, h.size(0) == 0
-        if ctx.empty:                        # no rows: nothing to launch (an empty tensor has no address)
-            ctx.shapes = (h.shape, a.shape)
-            return h.new_empty((0, m))
-        ks, op, degree, k, _ = geom
-        b, wi = _spline_basis(a, ks, op, degree)
-        y = _spline_fwd(g, b, wi, h, k, m, mean, base, relu)
-        ctx.save_for_backward(h, b, wi, a if ctx.needs_input_grad[2] else None, y if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        need = ctx.needs_input_grad
-        if ctx.empty:
-            hs, as_ = ctx.shapes
-            return (None, gy.new_zeros(hs) if need[1] else None, gy.new_zeros(as_) if need[2] else None,
-                    gy.new_zeros(gy.shape) if need[3] else None, None, None, None, None)
-        h, b, wi, a, y = ctx.saved_tensors
-        ks, op, degree, k, _ = ctx.geom
-        if ctx.relu:
-            gy, _ = _mask_and_bias_grad(_grad_layout(gy, 0), y, None, False)
-        else:
-            gy = _sage_grad(gy)
-        gh = _spline_bwd_h(ctx.g, b, wi, gy, k, ctx.mean) if need[1] else None
-        ga = None
-        if need[2]:
-            ga = _spline_bwd_a(_spline_bwd_b(ctx.g, wi, h, gy, k, ctx.mean), a, ks, op, degree)
-        return None, gh, ga, gy if need[3] else None, None, None, None, None
-
-
-def spline_aggregate(g: Optional[GraphIndex], h: torch.Tensor, edge_attr: torch.Tensor, kernel_size, is_open_spline,
-                     degree: int = 1, reduce: str = "mean", base: Optional[torch.Tensor] = None,
-                     relu: bool = False) -> torch.Tensor:
-    """PyG ``SplineConv``'s aggregation (torch-spline-conv's basis and weighting): ``s_i = sum_{j->i} sum_s b_s(e_ji)
-    h[j, wi_s(e_ji)*M:+M]`` over the edges of ``g`` - a ``GraphIndex`` of one ``edge_index`` built with
-    ``self_loops=False, normalize=False``: the edge set as given, duplicates counting - with the ``S = (degree+1)^D``
-    basis products ``b_s`` and weight indices ``wi_s`` of INTEGRATION.md 1.9.  ``reduce="mean"`` divides by the
-    in-degree (duplicates counted; a row without edges is 0), ``"add"`` does not; then ``+ base`` (``[N, M]``, the root
-    term with its bias; None: none) and, with ``relu``, the ReLU - all in the gather's epilogue.  ``h``: float32
-    ``[N, K*M]``, column ``k*M + c`` weight matrix k, channel c, ``K`` the product of ``kernel_size``; ``edge_attr``:
-    float32 ``[E, D]`` in [0, 1] with rows in the order of that ``edge_index`` (outside [0, 1] the index wraps, NaN
-    propagates; nothing is validated by a host read).  ``kernel_size`` (D ints), ``is_open_spline`` (D bools) and
-    ``degree`` (1..3) are host values.  Caps: ``D <= 4``, ``S <= 64``, ``K <= 1024``, ``E*S < 2^31``, ``N*K*M < 2^31``
-    (``ValueError``).  All tensors on the graph's device; ``h``, ``edge_attr`` and ``base`` with unit inner stride
-    (column slices pass as they are).  One autograd node, differentiable in ``h``, ``edge_attr`` (two launches, skipped
-    when it needs no gradient) and ``base``; with ``relu`` the backward masks by ``y > 0``: ``relu'(0) = 0``, and ``M``
-    must be a width of the mask pass (``gmm_relu_ok``).  The gradient of ``edge_attr`` reads the endpoints from
-    ``g.edge_index`` at backward time: the edge list must stay unchanged until the backward has run.  ``N = 0``
-    returns an empty tensor without a launch (``g`` may then be None)."""
-    if not isinstance(reduce, str) or reduce not in SPLINE_REDUCES:
-        raise ValueError(f"spline_aggregate: reduce must be 'mean' or 'add', got {reduce!r}")
-    h, edge_attr = resolve(h), resolve(edge_attr)
-    for name, t in (("h", h), ("edge_attr", edge_attr)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"spline_aggregate: {name} must be a tensor, got {type(t).__name__}")
-    geom = spline_geometry(kernel_size, is_open_spline, degree,
-                           None if isinstance(kernel_size, (list, tuple, torch.Tensor)) else
-                           (edge_attr.size(1) if edge_attr.dim() == 2 else -1))
-    ks, _, _, k, s = geom
-    d = len(ks)
-    if h.dim() != 2 or h.dtype != torch.float32 or h.size(1) == 0 or h.size(1) % k:
-        raise ValueError(f"spline_aggregate: h must be a float32 [N, K*M] tensor with K = {k}, M >= 1, got "
-                         f"{tuple(h.shape)} {h.dtype}")
-    m = h.size(1) // k
-    if edge_attr.dim() != 2 or edge_attr.dtype != torch.float32 or edge_attr.size(1) != d:
-        raise ValueError(f"spline_aggregate: edge_attr must be a float32 [E, {d}] tensor, got "
-                         f"{tuple(edge_attr.shape)} {edge_attr.dtype}")
-    if edge_attr.size(0) * s >= 2 ** 31:
-        raise ValueError(f"spline_aggregate: E*S = {edge_attr.size(0)}*{s} must stay below 2^31")
-    if h.size(0) * k * m >= 2 ** 31:
-        raise ValueError(f"spline_aggregate: N*K*M = {h.size(0)}*{k}*{m} must stay below 2^31")
-    if base is not None:
-        base = resolve(base)
-        if not isinstance(base, torch.Tensor) or base.dim() != 2 or base.dtype != torch.float32 or \
-                base.shape != (h.size(0), m):
-            raise ValueError(f"spline_aggregate: base must be a float32 [{h.size(0)}, {m}] tensor (or None)")
-    if relu and not gmm_relu_ok(m):
-        raise ValueError(f"spline_aggregate: relu=True needs M to be a multiple of 4 that divides 1024, got {m}; apply "
-                         "the ReLU behind the call")
-    _require_cuda(h, "h")
-    for name, t in (("edge_attr", edge_attr), ("base", base)):
-        if t is not None:
-            _require_cuda(t, name)
-            if t.device != h.device:
-                raise RuntimeError(f"spline_aggregate: h is on {h.device} but {name} is on {t.device}")
-    mean = reduce == "mean"
-    if h.size(0) == 0:
-        if edge_attr.size(0) != 0:
-            raise ValueError(f"spline_aggregate: edge_attr has {edge_attr.size(0)} rows but h has no node")
-        return _SplineAggFn.apply(None, h, edge_attr, base, geom, m, mean, bool(relu))
-    if g is None:
-        raise ValueError("spline_aggregate: g may be None only for an h without rows")
-    if g.self_loops or g.normalize or g.edge_index is None or g.fwd.row_offset or g.bwd.row_offset:
-        raise ValueError("spline_aggregate: the graph must be built from one edge_index with self_loops=False, "
-                         "normalize=False (not a merged adjacency or a row window of one)")
-    if g.device != h.device:
-        raise RuntimeError(f"spline_aggregate: h is on {h.device} but the graph is on {g.device}")
-    if g.num_nodes != h.size(0):
-        raise ValueError(f"spline_aggregate: h has {h.size(0)} rows but the graph has {g.num_nodes} nodes")
-    if g.num_input_edges != edge_attr.size(0):
-        raise ValueError(f"spline_aggregate: edge_attr has {edge_attr.size(0)} rows but the graph has "
-                         f"{g.num_input_edges} edges")
-
-    def rows(t):
-        # unit inner stride and rows that do not overlap (an expanded operand is copied); a column slice passes as it is
-        return t.contiguous() if (t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)) else t
-    return _SplineAggFn.apply(g, rows(h), rows(edge_attr), rows(base) if base is not None else None, geom, m, mean,
-                              bool(relu))
+# These imports are the LAST statements of the module: a layer module imports ``ops`` (for ``hop``, ``_direct_sink`` and
+# the switches above, which it reads as ``ops.NAME`` at call time), so everything it may ask for has to exist by now.
+# Each list is the module's public names, then the launchers (one per C entry) that the kernel tests and the tools under
+# ``tools/`` call by name as ``ops._<launcher>``; the autograd Functions and the other helpers stay in their module.
+from .layers.gnn import (  # noqa: E402,F401
+    fused_gnn_ok, gat_aggregate, gat_conv, gcn_aggregate,
+    _agg_bias_act, _gat_edge_softmax)
+from .layers.gat_heads import (  # noqa: E402,F401
+    GAT_EDGE_MAX_DIM, gat_edge_fill, gat_edge_fold, gat_heads_aggregate, gat_heads_conv, gat_heads_edge_conv,
+    gat_heads_fused_ok,
+    _edge_softmax_bwd, _edge_softmax_fwd, _edge_term_bwd, _edge_term_fwd, _heads_agg, _heads_alpha_bwd, _heads_alpha_fwd,
+    _heads_gather, _heads_sddmm, _heads_segment_sum, _heads_softmax_bwd, _heads_softmax_fwd, _heads_spread)
+from .layers.gatv2 import (  # noqa: E402,F401
+    gatv2_conv,
+    _gatv2_softmax_bwd, _gatv2_softmax_fwd, _gatv2_source_bwd)
+from .layers.transformer import (  # noqa: E402,F401
+    transformer_conv,
+    _tconv_scale, _tconv_softmax_bwd, _tconv_softmax_fwd, _tconv_source_bwd)
+from .layers.sage import (  # noqa: E402,F401
+    aggregate,
+    _sage_max_bwd, _sage_max_fwd, _sage_mean_bwd, _sage_mean_fwd)
+from .layers.gine import (  # noqa: E402,F401
+    gine_aggregate,
+    _gine_bwd_e, _gine_bwd_x, _gine_fwd)
+from .layers.edge import (  # noqa: E402,F401
+    EDGE_REDUCE_MODES, edge_aggregate, edge_pairs,
+    _edge_pair_bwd, _edge_pair_fwd, _edge_reduce_bwd, _edge_reduce_fwd)
+from .layers.pointnet import (  # noqa: E402,F401
+    pointnet_aggregate, pointnet_graph, pointnet_pairs,
+    _pointnet_pair_bwd, _pointnet_pair_fwd, _pointnet_reduce_bwd)
+from .layers.cheb import (  # noqa: E402,F401
+    CHEB_MODES, cheb_basis, cheb_diagonal, cheb_lambda,
+    _cheb_hop, _cheb_norm)
+from .layers.gmm import (  # noqa: E402,F401
+    GMM_MAX_D, GMM_MAX_K, GMM_REDUCES, gmm_aggregate, gmm_relu_ok,
+    _gmm_bwd_h, _gmm_bwd_params, _gmm_bwd_w, _gmm_fwd, _gmm_weights)
+from .layers.spline import (  # noqa: E402,F401
+    SPLINE_MAX_D, SPLINE_MAX_K, SPLINE_MAX_S, SPLINE_REDUCES, spline_aggregate, spline_geometry,
+    _spline_basis, _spline_bwd_a, _spline_bwd_b, _spline_bwd_h, _spline_fwd)

@@ -174,7 +174,7 @@ def _by_source(nbr: Tensor, nx: int):
 
 
 def _grad_rows(g: Tensor) -> Tensor:
-    """The incoming gradient with unit inner stride and rows that do not overlap (``ops._sage_grad``)."""
+    """The incoming gradient with unit inner stride and rows that do not overlap (``layers.sage._sage_grad``)."""
     if g.stride(1) != 1:
         g = g.contiguous()
     return g if g.size(0) <= 1 or g.stride(0) >= g.size(1) else g.contiguous()
@@ -227,7 +227,7 @@ class _KnnInterpolateFn(torch.autograd.Function):
 
 
 def _feature_rows(t: Tensor) -> Tensor:
-    """unit inner stride and rows that do not overlap; a column slice passes as it is (``ops._edge_rows``)"""
+    """unit inner stride and rows that do not overlap; a column slice passes as it is (``_host._rows``)"""
     if (t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)):
         return t.contiguous()
     return t

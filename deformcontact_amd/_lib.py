@@ -32,6 +32,9 @@ _SIGNATURES = {
     "dc_graph_build_plan": (c_int, [c_int64, c_int64, c_int, POINTER(c_int), POINTER(c_int)]),
     "dc_graph_build_segmented": (c_int, [_vp, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), c_int,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dc_hop_chain_image_bytes": (c_int64, [c_int64]),
+    "dc_graph_build_segmented_image": (c_int, [_vp, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), c_int,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dc_graph_build_segmented_loops": (c_int, [_vp, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), c_int,
                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dc_attn_flash_prep": (c_int, [_vp, c_int64, c_int64, _vp, _vp, _vp]),
@@ -48,6 +51,8 @@ _SIGNATURES = {
     "dc_hop_chain_lds_request": (c_int64, []),
     "dc_hop_chain_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, POINTER(c_int64), c_int, _vp, c_int64, c_int64, c_int64,
                                  c_int, c_int, c_int, _vp, c_int, _vp]),
+    "dc_hop_chain_image_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, POINTER(c_int64), c_int, _vp, c_int64, c_int64,
+                                       c_int64, c_int, c_int, c_int, _vp, c_int, _vp, _vp]),
     "dc_spmm_f32_bias_act": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int, _vp, c_int64, c_int64, c_int64, _vp]),
     "dc_colsum_workspace_bytes": (c_int64, [c_int64, c_int64, c_int]),
     "dc_mask_colsum_f32": (c_int, [_vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp, c_int64, _vp, c_int,

@@ -460,6 +460,12 @@ constexpr int kSegEdges = DC_SEG_MAX_EDGES;
 
 constexpr int kSegChunk = 96;                 // graphs per launch (their offsets travel as kernel arguments)
 
+// The hop chain's table image of one side (dc_hop_chain_image_f32): ids [N][8] uint16 | {first edge, degree} [N] int2 |
+// dis [N + 1] float.  Row n0 + r of every table belongs to row r of the graph that starts at node n0, so a chain workgroup
+// fetches its graph's tables as three contiguous pieces.  Unused id slots hold kChainPadId: the chain kernel replaces it by
+// the index of ITS row of zeros (which depends on its row capacity) while it copies the table into LDS.
+constexpr uint16_t kChainPadId = 0xffff;
+
 struct SegBuild {
     const int64_t *src, *dst;            // rows 0 / 1 of edge_index
     int32_t node_ptr[kSegChunk + 1];     // offsets of this launch's graphs (host-validated: ascending, within caps)
@@ -469,6 +475,7 @@ struct SegBuild {
     int32_t *ptr[2], *other[2], *perm[2];
     float *w[2];
     int32_t *status;
+    char *image[2];                      // the hop chain's table image of each side (dc_hop_chain_image_f32), or null
 };
 
 __global__ void __launch_bounds__(1024)
@@ -533,6 +540,7 @@ k_build_segment(SegBuild b) {
     __syncthreads();
     int32_t *__restrict__ other = b.other[side], *__restrict__ perm = b.perm[side];
     float *__restrict__ w = b.w[side];
+    char *__restrict__ img = b.image[side];
     for (int p = tid; p < ne; p += 1024) {
         const int e = tmp[p], k = key16[e], o = oth16[e];
         const int beg = excl[k], end = excl[k + 1];
@@ -545,6 +553,23 @@ k_build_segment(SegBuild b) {
             const int sl = side ? k : o, dl = side ? o : k;      // gcn_norm: dis[source] * 1 * dis[destination]
             w[out] = inv_sqrt_count(degin[sl]) * 1.0f * inv_sqrt_count(degin[dl]);
         }
+        // the chain's id table: the row's first eight neighbours, local to the graph (2 bytes each; neighbouring threads
+        // write neighbouring slots).  A flagged edge sits on node 0 here as it does in `other`.
+        if (img && rank < 8) reinterpret_cast<uint16_t *>(img)[8 * (int64_t)(n0 + k) + rank] = (uint16_t)o;
+    }
+    if (img) {
+        // the rest of the image, row by row: pad ids behind the row's last neighbour, {first edge, degree} and
+        // dis = in-degree^-1/2 - what k_hop_chain_gcn derives from ptr / other / deg_ptr when it has no image
+        uint16_t *ids = reinterpret_cast<uint16_t *>(img);
+        int2 *bounds = reinterpret_cast<int2 *>(img + 16 * b.N);
+        float *dis = reinterpret_cast<float *>(img + 24 * b.N);
+        for (int i = tid; i < nn; i += 1024) {
+            const int beg = excl[i], d = excl[i + 1] - beg;
+            for (int j = d; j < 8; ++j) ids[8 * (int64_t)(n0 + i) + j] = kChainPadId;
+            bounds[n0 + i] = make_int2(e0 + beg, d);
+            dis[n0 + i] = inv_sqrt_count(degin[i]);
+        }
+        if (tid == 0 && b.last && seg == b.nseg - 1) dis[b.N] = 0.0f;     // the entry a pad id stands for
     }
 }
 
@@ -1218,6 +1243,10 @@ extern "C" int dc_graph_build_parts(const int64_t *const *edge_index_parts, cons
     return run_build(b, 2, stream, "dc_graph_build_parts");
 }
 
+// the images dc_graph_build_segmented_image asks for: set around its call of build_segmented, whose signature (and with it
+// the name of its launch sites) stays what it was
+static thread_local void *seg_image[2] = {nullptr, nullptr};
+
 static int build_segmented(int self_loops, const int64_t *edge_index, int64_t E, int64_t N,
                            const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
                            int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
@@ -1248,6 +1277,7 @@ static int build_segmented(int self_loops, const int64_t *edge_index, int64_t E,
     b.src = edge_index, b.dst = edge_index + E, b.E = E, b.N = N, b.status = status;
     b.ptr[0] = ptr_f, b.other[0] = other_f, b.perm[0] = perm_f, b.w[0] = w_f;
     b.ptr[1] = ptr_b, b.other[1] = other_b, b.perm[1] = perm_b, b.w[1] = w_b;
+    b.image[0] = static_cast<char *>(seg_image[0]), b.image[1] = static_cast<char *>(seg_image[1]);
     for (int first = 0; first < nseg; first += kSegChunk) {
         const int cnt = nseg - first < kSegChunk ? nseg - first : kSegChunk;
         for (int i = 0; i <= cnt; ++i) {
@@ -1268,6 +1298,26 @@ extern "C" int dc_graph_build_segmented(const int64_t *edge_index, int64_t E, in
                                         int32_t *status, dc_stream_t stream) {
     return build_segmented(0, edge_index, E, N, node_ptr_host, edge_ptr_host, nseg, ptr_f, other_f, perm_f, w_f, ptr_b,
                            other_b, perm_b, w_b, status, stream);
+}
+
+extern "C" int64_t dc_hop_chain_image_bytes(int64_t N) {
+    if (N < 0) return DC_EINVAL;
+    return align16(16 * N + 8 * N + 4 * (N + 1));
+}
+
+extern "C" int dc_graph_build_segmented_image(const int64_t *edge_index, int64_t E, int64_t N,
+                                              const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                                              int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
+                                              int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
+                                              void *image_f, void *image_b, int32_t *status, dc_stream_t stream) {
+    DC_REQUIRE(image_f && image_b, "dc_graph_build_segmented_image: null image");
+    DC_REQUIRE((((uintptr_t)image_f | (uintptr_t)image_b) & 15) == 0,
+               "dc_graph_build_segmented_image: images must be 16-byte aligned");
+    seg_image[0] = image_f, seg_image[1] = image_b;
+    const int rc = build_segmented(0, edge_index, E, N, node_ptr_host, edge_ptr_host, nseg, ptr_f, other_f, perm_f, w_f,
+                                   ptr_b, other_b, perm_b, w_b, status, stream);
+    seg_image[0] = seg_image[1] = nullptr;
+    return rc;
 }
 
 extern "C" int dc_graph_build_segmented_loops(const int64_t *edge_index, int64_t E, int64_t N,

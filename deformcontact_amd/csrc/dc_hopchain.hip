@@ -56,6 +56,8 @@ struct ChainParams {
     float *rowmax;
     int32_t cap;                      // elements of other / w (range check of the 16-byte id / weight loads)
     int F, nslices, K, src0, dir, rm_mode, nseg;
+    const char *image;                // k_hop_chain_gcn: the table image of this set (dc_graph_build_segmented_image) or null
+    int64_t N;                        // rows of the image's tables
     int32_t node_ptr[kChainGraphs + 1];
 };
 
@@ -374,14 +376,50 @@ k_hop_chain_gcn(ChainParams p) {
         reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0x7fc00000u, 0x7fc00000u, 0x7fc00000u, 0x7fc00000u);
     __syncthreads();
 #endif
-    // prologue, by wave role: waves 8-15 issue ALL the LDS-DMA of the slice (one instruction = 8 rows x 128 B, contiguous
+    // prologue without a table image, by wave role: waves 8-15 issue ALL the LDS-DMA of the slice (one instruction = 8 rows x 128 B, contiguous
     // in LDS), waves 0-7 build the tables.  hipcc makes a wave with LDS-DMA in flight wait for vmcnt(0) before each of
     // its own LDS accesses: with both jobs in every wave the tables' loads were only issued once the slice had landed.
     const __amdgpu_buffer_rsrc_t ro =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(p.other), 0, p.cap * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w), 0, p.cap * 4, 0x00020000);
-    if (wid >= 8) {
+    if (p.image) {
+        // tables from the image the segmented build left (a uniform branch): row threadIdx.x of the three tables with one
+        // coalesced load each, issued BEFORE the slice's LDS-DMA, which all 16 waves then share (wave w brings in its own
+        // rows).  The LDS writes below sit behind the compiler's vmcnt(0) for the DMA - which the barrier needs anyway.
+        const int r = threadIdx.x;
+        const bool live = r < nn;
+        // (unconditional loads - rows past the graph's end read entry n0, which every table has: n0 <= N - and the choice
+        // is made when the values are used: a load under a branch made the wave wait for it before it issued the DMA)
+        const int64_t ri = n0 + (live ? r : 0);
+        uint4 iv = *reinterpret_cast<const uint4 *>(p.image + 16 * ri);
+        int2 bd = *reinterpret_cast<const int2 *>(p.image + 16 * p.N + 8 * ri);
+        float di = *reinterpret_cast<const float *>(p.image + 24 * p.N + 4 * ri);
+        const float *src = blk + (int64_t)p.src0 * p.F;
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) {
+            const int r0 = rwave + 8 * s;
+            if (r0 + grp < nn && !(DC_CHAIN_ABL & 8))
+                __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + (int64_t)(r0 + grp) * p.ld), DC_DMA_DST(smem + r0 * 128), 16, 0, 0);
+        }
+        if (threadIdx.x < 8)
+            *reinterpret_cast<float4 *>(smem + R * 128 + 16 * threadIdx.x) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < R) {
+            // the image's pad id -> this instantiation's row of zeros (row R, whose dis is 0)
+            if (!live) iv = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu), bd = make_int2(0, 0), di = 0.f;
+            const unsigned q[4] = {iv.x, iv.y, iv.z, iv.w};
+            unsigned o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned lo = q[j] & 0xffffu, hi = q[j] >> 16;
+                o[j] = (lo == 0xffffu ? (unsigned)R : lo) | (hi == 0xffffu ? (unsigned)R : hi) << 16;
+            }
+            *reinterpret_cast<uint4 *>(smem + kIds + 16 * r) = make_uint4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<int2 *>(smem + kBounds + 8 * r) = bd;
+            *reinterpret_cast<float *>(smem + kDis + 4 * r) = di;
+        }
+        if (r == R - 1) *reinterpret_cast<float *>(smem + kDis + 4 * R) = 0.f;
+    } else if (wid >= 8) {
         const float *src = blk + (int64_t)p.src0 * p.F;
 #pragma unroll
         for (int s = 0; s < 2 * STEPS; ++s) {
@@ -489,7 +527,14 @@ k_hop_chain_gcn(ChainParams p) {
             *reinterpret_cast<float4 *>(smem + (rwave + 8 * s + grp) * 128 + 16 * sub) = acc[s];
         lds_barrier();
     }
-    if (want_rm) publish_rowmax(pm, sub, STEPS, rwave + 8 * sub + grp, nn, p.rowmax + n0);
+    if (want_rm) {
+        // the lane's position once more, from the exec mask: kept from the prologue, `sub` and `grp` cost the 8-step form
+        // three registers it does not have - it spilled them, and the reload put a vmcnt(0), i.e. a wait for the last
+        // hop's stores, in front of the atomics
+        const int l2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const int sub2 = l2 & 7, grp2 = l2 >> 3;
+        publish_rowmax(pm, sub2, STEPS, rwave + 8 * sub2 + grp2, nn, p.rowmax + n0);
+    }
 #ifdef DC_CHAIN_POISON_END
     // diagnostic build (tools/r05): leave quiet NaNs behind in the slice, so that a LATER workgroup on this CU that reads LDS
     // it has not (yet) written cannot pass for data of the right magnitude; the prologue's timing stays what it is
@@ -611,10 +656,10 @@ extern "C" int64_t dc_hop_chain_lds_request(void) { return (int64_t)kChainLdsReq
 
 extern "C" int64_t dc_hop_chain_max_nodes(void) { return 4 * 128 * kChainSteps; }      // 8-column slices: 4,096 nodes
 
-extern "C" int dc_hop_chain_f32(const int32_t *ptr, const int32_t *other, const float *w, const int32_t *deg_ptr,
-                                int64_t cap, const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
-                                int64_t F, int K, int src_block, int dir, float *rowmax, int mode,
-                                dc_stream_t stream_) {
+static int hop_chain(const int32_t *ptr, const int32_t *other, const float *w, const int32_t *deg_ptr,
+                     int64_t cap, const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
+                     int64_t F, int K, int src_block, int dir, float *rowmax, int mode, const void *image,
+                     dc_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     DC_REQUIRE(N >= 0 && F >= 1 && K >= 0 && nseg >= 0, "dc_hop_chain_f32: negative size");
     if (N == 0 || K == 0 || nseg == 0) return DC_OK;
@@ -645,6 +690,7 @@ extern "C" int dc_hop_chain_f32(const int32_t *ptr, const int32_t *other, const 
     DC_REQUIRE(!deg_ptr || w, "dc_hop_chain_f32: deg_ptr describes the weights w - it cannot come without them");
     p.ptr = ptr, p.other = other, p.w = w, p.deg_ptr = deg_ptr, p.slab = slab, p.ld = ld, p.rowmax = rowmax, p.cap = (int32_t)cap;
     p.F = (int)F, p.nslices = (int)(F / kChainCols), p.K = K, p.src0 = src_block, p.dir = dir, p.rm_mode = mode;
+    p.image = static_cast<const char *>(image), p.N = N;         // (read by the LDS-table form alone)
     for (int s0 = 0; s0 < nseg; s0 += kChainGraphs) {
         const int cnt = nseg - s0 < kChainGraphs ? nseg - s0 : kChainGraphs;
         int64_t big = 0;
@@ -673,4 +719,21 @@ extern "C" int dc_hop_chain_f32(const int32_t *ptr, const int32_t *other, const 
         DC_REQUIRE(ok, "dc_hop_chain_f32: cannot reserve the kernel's LDS");
     }
     return check_launch("dc_hop_chain_f32");
+}
+
+extern "C" int dc_hop_chain_f32(const int32_t *ptr, const int32_t *other, const float *w, const int32_t *deg_ptr,
+                                int64_t cap, const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
+                                int64_t F, int K, int src_block, int dir, float *rowmax, int mode,
+                                dc_stream_t stream) {
+    return hop_chain(ptr, other, w, deg_ptr, cap, node_ptr_host, nseg, slab, ld, N, F, K, src_block, dir, rowmax, mode,
+                     nullptr, stream);
+}
+
+extern "C" int dc_hop_chain_image_f32(const int32_t *ptr, const int32_t *other, const float *w, const int32_t *deg_ptr,
+                                      int64_t cap, const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld,
+                                      int64_t N, int64_t F, int K, int src_block, int dir, float *rowmax, int mode,
+                                      const void *image, dc_stream_t stream) {
+    DC_REQUIRE(((uintptr_t)image & 15) == 0, "dc_hop_chain_image_f32: the image must be 16-byte aligned");
+    return hop_chain(ptr, other, w, deg_ptr, cap, node_ptr_host, nseg, slab, ld, N, F, K, src_block, dir, rowmax, mode,
+                     image, stream);
 }

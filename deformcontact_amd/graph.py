@@ -181,6 +181,14 @@ class GraphIndex:
         if self._layout is not None:
             nodes = self._layout[0]
             self._seg_max_nodes = max(nodes[i + 1] - nodes[i] for i in range(self._layout[1]))
+        #: the hop chain's table images of the two sides (``dc_graph_build_segmented_image`` writes them with the
+        #: adjacency, ``ops.hop_chain`` hands the walked side's to ``dc_hop_chain_image_f32``); None: the chain kernel builds
+        #: its tables itself (global / merged / self-loop builds)
+        self._chain_image = None
+        if self._segments is not None and self._layout is not None and self.normalize and not self.self_loops:
+            nb = int(_lib.lib().dc_hop_chain_image_bytes(n))
+            self._chain_image = (torch.empty(nb, dtype=torch.uint8, device=dev),
+                                 torch.empty(nb, dtype=torch.uint8, device=dev))
         self.rebuild()
         if validate:
             self.validate()
@@ -205,9 +213,15 @@ class GraphIndex:
                current_stream_ptr(self.device))
         if self._segments is not None:
             nptr, eptr, nseg = self._segments
-            build = _lib.lib().dc_graph_build_segmented_loops if self.self_loops else _lib.lib().dc_graph_build_segmented
-            rc = build(self.edge_index.data_ptr(), self.num_input_edges, self.num_nodes, nptr, eptr, nseg,
-                       *out[:9], out[11])
+            if self._chain_image is not None:
+                rc = _lib.lib().dc_graph_build_segmented_image(
+                    self.edge_index.data_ptr(), self.num_input_edges, self.num_nodes, nptr, eptr, nseg, *out[:8],
+                    self._chain_image[0].data_ptr(), self._chain_image[1].data_ptr(), out[8], out[11])
+            else:
+                build = (_lib.lib().dc_graph_build_segmented_loops if self.self_loops
+                         else _lib.lib().dc_graph_build_segmented)
+                rc = build(self.edge_index.data_ptr(), self.num_input_edges, self.num_nodes, nptr, eptr, nseg,
+                           *out[:9], out[11])
             _lib.check(rc, "dc_graph_build_segmented")
         elif self.parts is not None:
             import ctypes
@@ -277,6 +291,7 @@ class GraphIndex:
         out = [self._status, self._workspace]
         for adj in (self.fwd, self.bwd):
             out += [t for t in (adj.ptr, adj.other, adj.perm, adj.w) if t is not None]
+        out += list(self._chain_image or ())
         for entry in getattr(self, "_hop_cache", {}).values():
             out += [t for t in entry[:2] if t is not None]
         return out

@@ -237,10 +237,15 @@ def hop_chain(g, adj: SortedAdjacency, slab: torch.Tensor, f: int, k: int, weigh
     w = adj.w if weighted else None
     # the adjacency's weights are gcn_norm's (graph.GraphIndex builds nothing else): tell the kernel so
     deg = g.fwd.ptr if (HOP_CHAIN_GCN and w is not None and g.normalize and not g.self_loops) else None
-    rc = _lib.lib().dc_hop_chain_f32(
+    # the tables of the walked side as the segmented build left them (None: the kernel builds them in every workgroup)
+    images = getattr(g, "_chain_image", None)
+    image = None
+    if images is not None and deg is not None:
+        image = images[0] if adj is g.fwd else images[1] if adj is g.bwd else None
+    rc = _lib.lib().dc_hop_chain_image_f32(
         adj.ptr.data_ptr(), adj.other.data_ptr(), _ptr(w), _ptr(deg), adj.other.numel(),
         nptr, nseg, slab.data_ptr(), slab.stride(0), slab.size(0), f, k, int(src_block), int(direction),
-        _ptr(rowmax), int(rowmax_mode), current_stream_ptr(slab.device))
+        _ptr(rowmax), int(rowmax_mode), _ptr(image), current_stream_ptr(slab.device))
     _lib.check(rc, "dc_hop_chain_f32")
 
 

@@ -146,6 +146,21 @@ int dc_graph_build_segmented(const int64_t *edge_index, int64_t E, int64_t N,
                              int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
                              int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
                              int32_t *status, dc_stream_t stream);
+/* dc_graph_build_segmented that also writes, per side, the table image dc_hop_chain_image_f32 reads instead of
+ * deriving its LDS tables from ptr / other / deg_ptr in every workgroup: the same launch, no more LDS, no atomics.
+ * An image holds dc_hop_chain_image_bytes(N) bytes (16-byte aligned):
+ *     ids    [N][8] uint16   the first eight neighbours of every row as ids local to its graph, in `other` order;
+ *                            slots behind the row's last neighbour hold 0xffff
+ *     bounds [N][2] int32    {ptr[row], ptr[row + 1] - ptr[row]}
+ *     dis    [N + 1] float   in-degree^-1/2 (0 for degree 0) of every node; entry N, which a pad id stands for, is 0
+ * each table at its offset in that order.  Values are those the chain kernel computes itself, bit for bit (an edge the
+ * build flags sits on its graph's node 0 in the image as in `other`). */
+int64_t dc_hop_chain_image_bytes(int64_t N);
+int dc_graph_build_segmented_image(const int64_t *edge_index, int64_t E, int64_t N,
+                                   const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                                   int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
+                                   int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
+                                   void *image_f, void *image_b, int32_t *status, dc_stream_t stream);
 /* The self_loops = 1 form (the host layer takes it for small batches of GATConv(edge_dim) only), same arguments and caps; output arrays hold E + N entries.
  * Input self loops are dropped and the loop of node i is appended with edge id E + i, last in its group; the edge count
  * is ptr[N].  Still one launch per 96 graphs and no workspace: every workgroup counts the self loops among the input
@@ -332,6 +347,14 @@ int dc_hop_chain_f32(const int32_t *ptr, const int32_t *other, const float *w, c
                      int64_t cap, const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
                      int64_t F, int K, int src_block, int dir, float *rowmax, int mode,
                      dc_stream_t stream);
+/* dc_hop_chain_f32 with the table image of the set it walks (image_f of dc_graph_build_segmented_image for the
+ * by-destination set, image_b for the transposed one): with deg_ptr != NULL and 32-column slices every workgroup copies
+ * its graph's tables from the image instead of building them from ptr / other / deg_ptr; same blocks and row maxima,
+ * bit for bit.  image == NULL, or a launch that does not take the LDS-table form: exactly dc_hop_chain_f32. */
+int dc_hop_chain_image_f32(const int32_t *ptr, const int32_t *other, const float *w, const int32_t *deg_ptr,
+                           int64_t cap, const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
+                           int64_t F, int K, int src_block, int dir, float *rowmax, int mode, const void *image,
+                           dc_stream_t stream);
 
 /* ---- the dense block over bf16-STORED features (BASELINE.json configs[4]) ------------------
  * out[N,Fo] = act(A[N,K] . W[Fo,K]^T + bias) with A and W bf16 (uint16 bit patterns, K-contiguous,

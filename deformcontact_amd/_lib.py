@@ -1,4 +1,4 @@
-"""ctypes binding of ``libdeformcontact_hip.so`` (the C ABI in ``include/deformcontact.h``).
+"""ctypes binding of ``libdeformcontact_hip.so``, derived from the C ABI's header ``include/deformcontact.h``.
 
 There is deliberately NO fallback: if the library is missing or fails to load,
 every op raises.  The CPU oracle under ``oracle/`` is test infrastructure and is
@@ -7,260 +7,90 @@ never imported from here.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+import re
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint16, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libdeformcontact_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deformcontact.h")
 
 _lib = None
-
-_vp = c_void_p
-_SIGNATURES = {
-    "dc_version": (c_int, []),
-    "dc_last_error": (c_char_p, []),
-    "dc_stream_capture_id": (c_int64, [_vp]),
-    "dc_csr_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "dc_csr_build": (c_int, [_vp, c_int64, c_int64, c_int, c_int, _vp, _vp, _vp, _vp, _vp, _vp,
-                             _vp, c_int64, _vp]),
-    "dc_graph_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "dc_graph_build": (c_int, [_vp, c_int64, c_int64, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                               _vp, _vp, c_int64, _vp]),
-    "dc_graph_build_parts": (c_int, [POINTER(_vp), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int,
-                                     c_int64, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_int64,
-                                     _vp]),
-    "dc_graph_build_plan": (c_int, [c_int64, c_int64, c_int, POINTER(c_int), POINTER(c_int)]),
-    "dc_graph_build_segmented": (c_int, [_vp, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), c_int,
-                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dc_hop_chain_image_bytes": (c_int64, [c_int64]),
-    "dc_graph_build_segmented_image": (c_int, [_vp, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), c_int,
-                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dc_graph_build_segmented_loops": (c_int, [_vp, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64), c_int,
-                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dc_attn_flash_prep": (c_int, [_vp, c_int64, c_int64, _vp, _vp, _vp]),
-    "dc_attn_flash_ds": (c_int, [_vp, c_int64, _vp, _vp, c_int64, _vp, _vp, _vp, _vp, _vp, _vp, c_int64, c_int64,
-                                 c_int64, c_int64, _vp, _vp, c_int64, _vp, _vp, _vp, _vp]),
-    "dc_tag_linear_fwd_h2p_corr": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, c_int64, _vp, _vp,
-                                           _vp]),
-    "dc_tag_linear_bwd_dw_h2_corr": (c_int, [_vp, c_int64, _vp, _vp, POINTER(_vp), POINTER(c_int64), c_int, POINTER(_vp),
-                                             c_int, c_int64, c_int, _vp, c_int64, c_int64, c_int64, c_int64, _vp, _vp,
-                                             _vp]),
-    "dc_attn_flash_fwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, c_int64, _vp,
-                                  c_int64, _vp, _vp]),
-    "dc_hop_chain_max_nodes": (c_int64, []),
-    "dc_hop_chain_lds_request": (c_int64, []),
-    "dc_hop_chain_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, POINTER(c_int64), c_int, _vp, c_int64, c_int64, c_int64,
-                                 c_int, c_int, c_int, _vp, c_int, _vp]),
-    "dc_hop_chain_image_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, POINTER(c_int64), c_int, _vp, c_int64, c_int64,
-                                       c_int64, c_int, c_int, c_int, _vp, c_int, _vp, _vp]),
-    "dc_spmm_f32_bias_act": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_colsum_workspace_bytes": (c_int64, [c_int64, c_int64, c_int]),
-    "dc_mask_colsum_f32": (c_int, [_vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp, c_int64, _vp, c_int,
-                                   _vp]),
-    "dc_gat_alpha_fwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, c_int64, c_int64, _vp]),
-    "dc_gat_alpha_bwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, _vp, c_int64, _vp, _vp,
-                                 c_int, _vp]),
-    "dc_spmm_f32_pack": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_spmm_f32_pack_wprep": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, c_int64,
-                                       POINTER(_vp), c_int, _vp, _vp]),
-    "dc_spmm_f32_window": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
-                                   c_int64, c_int64, _vp]),
-    "dc_spmm_f32_rowmax_window": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
-                                          c_int64, _vp, c_int, c_int64, _vp]),
-    "dc_tag_grouped_weight_prep": (c_int, [POINTER(_vp), c_int, c_int, c_int64, c_int64, POINTER(_vp),
-                                           POINTER(_vp), POINTER(_vp), POINTER(_vp), _vp]),
-    "dc_tag_grouped_fwd_h2p": (c_int, [_vp, c_int64, c_int, POINTER(c_int64), POINTER(c_int64), c_int64,
-                                       POINTER(_vp), POINTER(_vp), c_int, _vp, c_int64, c_int64, c_int64, _vp,
-                                       POINTER(_vp), _vp]),
-    "dc_tag_grouped_mask_grad": (c_int, [POINTER(_vp), POINTER(c_int64), c_int, POINTER(c_int64),
-                                         POINTER(c_int64), c_int64, _vp, c_int64, _vp, c_int64, c_int64, _vp,
-                                         _vp, _vp]),
-    "dc_tag_grouped_bwd_dw_workspace_bytes": (c_int64, [POINTER(c_int64), c_int, c_int64, c_int64, c_int]),
-    "dc_tag_grouped_bwd_dw_h2": (c_int, [_vp, c_int64, POINTER(_vp), POINTER(c_int64), c_int, c_int,
-                                         POINTER(c_int64), POINTER(c_int64), c_int64, POINTER(_vp),
-                                         POINTER(_vp), c_int, _vp, c_int64, c_int64, c_int64, _vp, _vp, _vp]),
-    "dc_generic_dense_launches": (c_int64, [c_int]),
-    "dc_kernel_trace": (None, [c_int]),
-    "dc_kernel_trace_dump": (c_int64, [c_char_p, c_int64]),
-    "dc_launch_sites_dump": (c_int64, [c_char_p, c_int64]),
-    "dc_launch_coverage": (None, [c_int]),
-    "dc_launch_reached_dump": (c_int64, [c_char_p, c_int64]),
-    "dc_hash_i64": (c_int, [_vp, c_int64, _vp, _vp]),
-    "dc_morton_codes": (c_int, [_vp, c_int64, c_int64, POINTER(c_float), POINTER(c_float), _vp, _vp]),
-    "dc_morton_order_workspace_bytes": (c_int64, [c_int64]),
-    "dc_morton_order": (c_int, [_vp, c_int64, c_int64, _vp, _vp, _vp, c_int64, _vp]),
-    "dc_relabel_edges": (c_int, [_vp, c_int64, _vp, c_int64, _vp, _vp]),
-    "dc_gather_rows": (c_int, [_vp, c_int64, _vp, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_invert_perm": (c_int, [_vp, _vp, _vp, c_int64, _vp]),
-    "dc_neighbors_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "dc_neighbors_fill": (c_int, [_vp, c_int64, c_int64, _vp, _vp, c_int64, c_int64, _vp, c_int, c_float, c_int, c_int,
-                                  _vp, _vp, _vp, c_int64, _vp]),
-    "dc_neighbors_compact_workspace_bytes": (c_int64, [c_int64]),
-    "dc_neighbors_compact": (c_int, [_vp, c_int, _vp, c_int64, c_int, _vp, c_int64, _vp, c_int64, _vp]),
-    "dc_neighbors_nd_fill": (c_int, [_vp, c_int64, c_int64, _vp, _vp, c_int64, c_int64, _vp, c_int64, c_int, c_int,
-                                     _vp, _vp, _vp]),
-    "dc_spmm_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
-                            c_int64, _vp]),
-    "dc_spmm_bf16": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
-                             c_int64, c_int, _vp]),
-    "dc_tag_linear_fwd_bf16": (c_int, [_vp, c_int64, _vp, _vp, c_int, _vp, c_int64, c_int, c_int64, c_int64,
-                                       c_int64, _vp]),
-    "dc_tag_mask_grad_bf16": (c_int, [_vp, c_int64, c_int, _vp, c_int64, c_int, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_tag_linear_bwd_dw_bf16_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
-    "dc_tag_linear_bwd_dw_bf16": (c_int, [_vp, c_int64, _vp, c_int64, c_int, POINTER(_vp), _vp, c_int, _vp, c_int64,
-                                          c_int64, c_int64, c_int64, _vp]),
-    "dc_to_bf16": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, c_int64, _vp, c_int64, _vp]),
-    "dc_contact_loss_workspace_bytes": (c_int64, [c_int64]),
-    "dc_contact_loss": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp, _vp,
-                                _vp, _vp, c_int64, _vp]),
-    "dc_tag_linear_fwd": (c_int, [POINTER(_vp), POINTER(c_int64), POINTER(_vp), c_int, _vp, c_int,
-                                  _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_tag_linear_bwd_dx": (c_int, [_vp, c_int64, _vp, c_int64, POINTER(_vp), c_int,
-                                     POINTER(_vp), POINTER(c_int64), c_int64, c_int64, c_int64,
-                                     _vp]),
-    "dc_tag_linear_fwd_split": (c_int, [POINTER(_vp), POINTER(c_int64), POINTER(_vp), c_int, _vp,
-                                        c_int, _vp, c_int64, c_int64, c_int64, c_int64, c_int, _vp]),
-    "dc_tag_linear_bwd_dx_split_workspace_bytes": (c_int64, [c_int64, c_int64, c_int]),
-    "dc_tag_linear_bwd_dx_split": (c_int, [_vp, c_int64, _vp, c_int64, POINTER(_vp), c_int,
-                                           POINTER(_vp), POINTER(c_int64), _vp, c_int64, c_int64,
-                                           c_int64, c_int64, c_int, _vp]),
-    "dc_tag_linear_bwd_dw_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
-    "dc_tag_linear_bwd_dw": (c_int, [_vp, c_int64, _vp, c_int64, POINTER(_vp), POINTER(c_int64),
-                                     c_int, POINTER(_vp), c_int, c_int64, _vp, c_int, _vp, c_int64,
-                                     c_int64, c_int64, c_int64, _vp]),
-    "dc_tag_linear_bwd_dw_split": (c_int, [_vp, c_int64, _vp, c_int64, POINTER(_vp),
-                                           POINTER(c_int64), c_int, POINTER(_vp), c_int, c_int64,
-                                           _vp, c_int, _vp, c_int64, c_int64, c_int64, c_int64,
-                                           c_int, _vp]),
-    "dc_tag_linear_fwd_h2": (c_int, [POINTER(_vp), POINTER(c_int64), POINTER(_vp), c_int, _vp,
-                                     c_int, _vp, c_int64, c_int64, c_int64, c_int64, _vp, _vp, _vp]),
-    "dc_tag_linear_bwd_dx_h2": (c_int, [_vp, c_int64, _vp, c_int64, POINTER(_vp), c_int,
-                                        POINTER(_vp), POINTER(c_int64), _vp, c_int64, c_int64,
-                                        c_int64, c_int64, _vp, _vp, _vp]),
-    "dc_tag_linear_bwd_dw_h2": (c_int, [_vp, c_int64, _vp, c_int64, POINTER(_vp),
-                                        POINTER(c_int64), c_int, POINTER(_vp), c_int, c_int64,
-                                        _vp, c_int, _vp, c_int64, c_int64, c_int64, c_int64,
-                                        _vp, _vp, _vp]),
-    "dc_tag_mask_grad": (c_int, [_vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp, _vp, _vp]),
-    "dc_tag_transpose_weights": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp]),
-    "dc_tag_linear_fwd_h2p_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
-    "dc_tag_linear_fwd_h2p": (c_int, [_vp, c_int64, _vp, _vp, c_int, _vp, c_int64, c_int64, c_int64, c_int64,
-                                      _vp, _vp, _vp, c_int64, _vp]),
-    "dc_tag_linear_fwd_h2p_exp": (c_int, [_vp, c_int64, _vp, _vp, c_int64, c_int64, c_int64, c_int64, _vp, _vp, _vp,
-                                          c_int64, _vp]),
-    "dc_tag_weight_prep": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp, _vp, _vp, _vp]),
-    "dc_tag_weight_prep_zero": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp, _vp, _vp, _vp, c_int64, _vp]),
-    "dc_rowabsmax_f32": (c_int, [_vp, c_int64, c_int64, c_int64, _vp, _vp]),
-    "dc_tag_weight_rowmax": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp]),
-    "dc_spmm_f32_rowmax": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
-                                   c_int64, _vp, c_int, _vp]),
-    "dc_tag_pack_input": (c_int, [_vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_tag_pack_weights": (c_int, [POINTER(_vp), c_int, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_tag_linear_fwd_narrow_ok": (c_int, [c_int64, c_int, c_int64, c_int64]),
-    "dc_tag_linear_fwd_narrow": (c_int, [_vp, c_int64, POINTER(_vp), c_int, c_int64, _vp, c_int, _vp, c_int64, c_int64,
-                                         c_int64, c_int64, _vp]),
-    "dc_tag_narrow_wimage": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp]),
-    "dc_tag_linear_fwd_narrow_img": (c_int, [_vp, c_int64, _vp, _vp, c_int, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_attn_softmax_rows": (c_int, [_vp, c_int64, c_int64, c_int64, c_int64, _vp, _vp]),
-    "dc_attn_exp_rows": (c_int, [_vp, c_int64, c_int64, c_int64, c_int64, _vp, _vp]),
-    "dc_attn_ds_rows": (c_int, [_vp, _vp, c_int64, c_int64, c_int64, _vp, _vp, _vp]),
-    "dc_adam_flat": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_float, c_float, c_float, c_float,
-                             c_int, _vp]),
-    "dc_compose_perm": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp]),
-    "dc_gat_edge_softmax_fwd": (c_int, [_vp, _vp, _vp, _vp, c_float, _vp, c_int64, _vp]),
-    "dc_gat_edge_softmax_bwd": (c_int, [_vp, _vp, _vp, _vp, c_float, _vp, _vp, _vp, _vp, c_int64,
-                                        _vp]),
-    "dc_sddmm_f32": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, _vp]),
-    "dc_segment_sum_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp]),
-    "dc_gather_f32": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp]),
-    "dc_gat_alpha_heads_fwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_gat_edge_softmax_heads_fwd": (c_int, [_vp, _vp, _vp, _vp, c_float, _vp, c_int64, c_int64, _vp]),
-    "dc_spmm_f32_heads_bias_act": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int, c_int, _vp, c_int64, c_int64,
-                                           c_int64, c_int64, _vp]),
-    "dc_sddmm_f32_heads": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_gat_edge_softmax_heads_bwd": (c_int, [_vp, _vp, _vp, _vp, c_float, _vp, _vp, _vp, _vp, c_int64, c_int64,
-                                              _vp]),
-    "dc_segment_sum_f32_heads": (c_int, [_vp, _vp, _vp, _vp, c_int64, c_int64, _vp]),
-    "dc_gather_f32_heads": (c_int, [_vp, _vp, _vp, _vp, c_int64, c_int64, _vp]),
-    "dc_spread_heads_f32": (c_int, [_vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_gat_alpha_heads_bwd": (c_int, [_vp, c_int64, _vp, _vp, _vp, _vp, _vp, c_int64, c_int64, c_int64, c_int64, _vp,
-                                       c_int64, _vp, _vp, c_int, _vp]),
-    "dc_gat_edge_attr_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int, c_float, _vp, _vp, c_int64, c_int64, c_int64,
-                                     c_int64, _vp]),
-    "dc_gat_edge_attr_softmax_fwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_float, _vp, c_int64, c_int64, _vp]),
-    "dc_gat_edge_attr_softmax_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_float, _vp, _vp, _vp, _vp, c_int64, c_int64,
-                                             _vp]),
-    "dc_gat_edge_attr_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
-    "dc_gat_edge_attr_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, _vp, c_int, _vp, c_int64, _vp, c_int64, c_int64,
-                                     c_int64, c_int64, c_int64, _vp, c_int64, _vp]),
-    "dc_gatv2_softmax_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_float, _vp, c_int64, c_int64, c_int64,
-                                     _vp]),
-    "dc_gatv2_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
-    "dc_gatv2_softmax_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_float, _vp, _vp, c_int64, _vp,
-                                     c_int, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_gatv2_source_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_float, _vp,
-                                    c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_tconv_softmax_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, c_float, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_tconv_softmax_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, c_float, _vp, _vp, c_int64, c_int64, c_int64,
-                                     c_int64, _vp]),
-    "dc_tconv_source_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64,
-                                    c_int64, c_int64, c_int64, _vp]),
-    "dc_sage_mean_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_sage_mean_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_sage_max_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_sage_max_bwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64,
-                                c_int64, _vp]),
-    "dc_gine_fwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_gine_bwd_x": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, _vp, c_int64, _vp, c_int64, c_int64,
-                              c_int64, _vp]),
-    "dc_gine_bwd_e": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64,
-                              c_int64, _vp]),
-    "dc_edge_pair_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_edge_pair_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_edge_reduce_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int, c_int64, c_int64, _vp]),
-    "dc_edge_reduce_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64,
-                                   c_int, c_int64, c_int64, c_int64, _vp]),
-    "dc_cheb_norm": (c_int, [_vp, _vp, _vp, _vp, c_int, c_float, _vp, _vp, _vp, c_int64, _vp]),
-    "dc_cheb_hop": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_float,
-                            c_int, c_int, c_int64, c_int64, _vp]),
-    "dc_gmm_weights": (c_int, [_vp, c_int64, _vp, _vp, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_gmm_fwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int, c_int, _vp, c_int64, c_int64, c_int64,
-                           c_int64, c_int64, _vp]),
-    "dc_gmm_bwd_h": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, c_int64,
-                             _vp]),
-    "dc_gmm_bwd_w": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_gmm_params_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
-    "dc_gmm_bwd_params": (c_int, [_vp, _vp, _vp, c_int64, _vp, _vp, _vp, c_int64, _vp, _vp, _vp, c_int64, c_int64,
-                                  c_int64, c_int64, _vp]),
-    "dc_spline_basis": (c_int, [_vp, c_int64, _vp, _vp, c_int64, _vp, _vp, c_int64, c_int64, _vp]),
-    "dc_spline_fwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int, c_int, _vp, c_int64, c_int64,
-                              c_int64, c_int64, c_int64, c_int64, _vp]),
-    "dc_spline_bwd_h": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64,
-                                c_int64, c_int64, _vp]),
-    "dc_spline_bwd_b": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64, c_int64,
-                                c_int64, _vp]),
-    "dc_spline_bwd_a": (c_int, [_vp, _vp, c_int64, _vp, _vp, c_int64, _vp, c_int64, c_int64, c_int64, _vp]),
-    "dc_fps_resident_points": (c_int64, []),
-    "dc_fps_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "dc_fps": (c_int, [_vp, c_int64, c_int64, _vp, _vp, c_int64, c_int64, _vp, _vp, c_int64, _vp, c_int64, _vp]),
-    "dc_knn_interpolate_fwd": (c_int, [_vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, _vp, c_int, _vp, c_int64, _vp, _vp,
-                                       c_int64, c_int64, c_int64, _vp]),
-    "dc_knn_interpolate_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, c_int, c_int64, c_int64, c_int64,
-                                       _vp]),
-    "dc_pointnet_pair_fwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int64, c_int64,
-                                     c_int64, c_int64, c_int, c_int, _vp]),
-    "dc_pointnet_pair_bwd": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp,
-                                     c_int64, c_int64, c_int64, c_int64, c_int64, c_int, _vp]),
-    "dc_pointnet_reduce_bwd": (c_int, [_vp, _vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp,
-                                       c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int, _vp]),
-    "dc_pool_fwd": (c_int, [_vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int, c_int64, c_int64, c_int64, _vp]),
-    "dc_pool_bwd": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, _vp, c_int64, c_int,
-                            c_int64, c_int64, c_int64, _vp]),
-}
 
 
 class DeformContactLibraryError(RuntimeError):
     pass
+
+
+# The binding is DERIVED from the header: an entry is its prototype there plus its definition in csrc/ (which the
+# compiler checks against the prototype), nothing in Python.  The type names a prototype may use:
+_C_TYPES = {"void": None, "int": c_int, "int32_t": c_int32, "int64_t": c_int64, "uint16_t": c_uint16,
+            "uint64_t": c_uint64, "float": c_float, "double": c_double, "dc_stream_t": c_void_p}
+
+
+def _ctype(decl: str, entry: str):
+    """The ctypes type of one parameter or return declaration: a scalar by value as itself; ``T *`` a device address
+    (``c_void_p``: callers pass ``tensor.data_ptr()``); ``DC_HOST T *`` a host array (``POINTER(T)``); a pointer to
+    pointers a host array of device addresses; ``char *`` host text.  Anything else is an error, not a guess."""
+    m = re.fullmatch(r"(DC_HOST\s+)?(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(?:\w+)?", decl)
+    host, base, stars = (m[1], m[2], m[3].count("*")) if m else (None, None, 0)
+    if base == "char" and stars == 1 and not host:
+        return c_char_p
+    if base not in _C_TYPES or (host and stars != 1) or (base == "void" and (host or not stars)):
+        raise DeformContactLibraryError(f"{HEADER_PATH}: {entry}: cannot bind `{decl}`")
+    if stars == 0:
+        return _C_TYPES[base]
+    if stars == 1:
+        return POINTER(_C_TYPES[base]) if host else c_void_p
+    return POINTER(c_void_p)
+
+
+def _parse_header(text: str):
+    """``({entry: (restype, argtypes)}, {"DC_*": int})`` of the header's ``extern "C"`` block.  Strict: besides comments,
+    preprocessor lines and the ``dc_stream_t`` typedef the block may hold only prototypes that map completely."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    block = re.search(r'extern "C" \{(.*)\}', text, flags=re.S)
+    if block is None:
+        raise DeformContactLibraryError(f'{HEADER_PATH}: no extern "C" block')
+    code, defines = [], {}
+    for line in block[1].splitlines():
+        if line.lstrip().startswith("#"):
+            m = re.fullmatch(r"\s*#\s*define\s+(DC_\w+)\s+\(?(-?\d+)\)?\s*", line)
+            if m:
+                defines[m[1]] = int(m[2])
+        else:
+            code.append(line)
+    signatures = {}
+    for stmt in " ".join(" ".join(code).split()).split(";"):
+        stmt = stmt.strip()
+        m = re.fullmatch(r"([\w *]+?)\b(dc_\w+) ?\(([^()]*)\)", stmt)
+        if m is None:
+            if stmt in ("", "typedef void *dc_stream_t"):
+                continue
+            raise DeformContactLibraryError(f"{HEADER_PATH}: not a prototype the binding understands: `{stmt[:160]}`")
+        ret, name, params = m[1].strip(), m[2], [p.strip() for p in m[3].split(",")]
+        signatures[name] = (None if ret == "void" else _ctype(ret, name),
+                            [] if params == ["void"] else [_ctype(p, name) for p in params])
+    return signatures, defines
+
+
+@functools.lru_cache(maxsize=None)
+def _header():
+    try:
+        with open(HEADER_PATH) as f:
+            text = f.read()
+    except OSError as e:
+        raise DeformContactLibraryError(
+            f"{HEADER_PATH} not found ({e.strerror}). deformcontact_amd derives its ctypes binding and its limits "
+            "from that header: use the package from its source tree.") from e
+    return _parse_header(text)
+
+
+def __getattr__(name):
+    if name == "DEFINES":           # {"DC_MAX_SEG": 4, ...}: the header's integer #define DC_* values, parsed on first use
+        return _header()[1]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def lib():
@@ -275,7 +105,7 @@ def lib():
             handle = ctypes.CDLL(SO_PATH)
         except OSError as e:  # pragma: no cover
             raise DeformContactLibraryError(f"cannot load {SO_PATH}: {e}") from e
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in _header()[0].items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:
@@ -362,15 +192,13 @@ def kernel_trace(on: bool) -> None:
 
 def kernel_trace_counts() -> dict:
     """``{kernel name: launches}`` recorded since ``kernel_trace(True)``."""
-    n = int(lib().dc_kernel_trace_dump(None, 0))
-    buf = ctypes.create_string_buffer(n + 1)
-    lib().dc_kernel_trace_dump(buf, n + 1)
     out = {}
-    for line in buf.value.decode().splitlines():
+    for line in _dump(lib().dc_kernel_trace_dump):
         name, _, cnt = line.rpartition(" ")
         out[name] = int(cnt)
     return out
 
 
 def exported_names():
-    return list(_SIGNATURES)
+    """Every entry the header declares, in its order (needs the header, not the library)."""
+    return list(_header()[0])

@@ -75,7 +75,7 @@ def _rowabsmax(L, t: torch.Tensor, st) -> torch.Tensor:
 #: compute unit) when d = dv = 256 - the shipped hidden width; ``DC_ATTN_FLASH=0``: the blocked three-launch form.
 #: Scores are bit-identical between the two (same products, same order), outputs agree to rounding.
 FLASH = os.environ.get("DC_ATTN_FLASH", "1") != "0"
-FLASH_D = 256
+FLASH_D = _lib.DEFINES["DC_ATTN_FLASH_D"]
 #: backward: P and dS for ALL rows from one two-sweep launch (``dc_attn_flash_ds``) followed by three large GEMMs,
 #: instead of six launches per 2,048-row block; needs 2 x Ns x Nr floats (6.4 GB per head at batch 32).
 #: ``DC_ATTN_FLASH_BWD=0``: the blocked backward.

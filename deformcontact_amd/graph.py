@@ -63,9 +63,11 @@ class SortedAdjacency:
     row_offset: int = 0
 
 
-#: every group of a merged node space starts at a multiple of this many rows (``DC_GROUP_ALIGN`` in
-#: include/deformcontact.h: no 128 / 256-row tile and no dW node chunk straddles two groups)
-GROUP_ALIGN = 256
+#: every group of a merged node space starts at a multiple of this many rows (no 128 / 256-row tile and no dW node
+#: chunk straddles two groups)
+GROUP_ALIGN = _lib.DEFINES["DC_GROUP_ALIGN"]
+#: the most edge_index parts of one merged adjacency (``GraphIndex.from_parts``)
+MAX_PARTS = _lib.DEFINES["DC_MAX_PARTS"]
 
 
 def _round_up(v: int, m: int) -> int:
@@ -83,8 +85,8 @@ class GraphIndex:
         #: merged (block-diagonal) adjacency: ``[(edge_index, num_nodes), ...]``; see ``from_parts``
         self.parts = None
         if parts is not None:
-            if not 1 <= len(parts) <= 4:
-                raise ValueError("GraphIndex.from_parts: 1..4 parts (DC_MAX_PARTS)")
+            if not 1 <= len(parts) <= MAX_PARTS:
+                raise ValueError(f"GraphIndex.from_parts: 1..{MAX_PARTS} parts (DC_MAX_PARTS)")
             eis = []
             for ei, n in parts:
                 _require_cuda(ei, "edge_index")
@@ -326,8 +328,8 @@ class GraphIndex:
         return self._bwd_to_fwd
 
 
-#: per-graph caps of the one-launch segmented build (include/deformcontact.h DC_SEG_MAX_NODES / DC_SEG_MAX_EDGES)
-SEG_MAX_NODES, SEG_MAX_EDGES = 4096, 16384
+#: per-graph caps of the one-launch segmented build
+SEG_MAX_NODES, SEG_MAX_EDGES = _lib.DEFINES["DC_SEG_MAX_NODES"], _lib.DEFINES["DC_SEG_MAX_EDGES"]
 SEGMENTED_BUILD = True
 #: graphs x input edges up to which the self-loop form of the segmented build is taken (GraphIndex.__init__).  Measured
 #: (profiles/r08/build_time.json): 24 vs 28 us of the global pipeline at 2 graphs x 12k edges, 32 vs 32 at 8 x 49k

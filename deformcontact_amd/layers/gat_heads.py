@@ -222,7 +222,7 @@ def gat_heads_conv(g: GraphIndex, h, att_src, att_dst, bias, slope: float, relu:
 # folded M [D, H] formed by ordinary torch ops OUTSIDE the Functions below, so autograd turns their gM into the
 # gradients of lin_edge.weight and att_edge.  One launcher per C entry.
 # --------------------------------------------------------------------------- #
-GAT_EDGE_MAX_DIM = 64              # DC_GAT_EDGE_MAX_DIM of include/deformcontact.h
+GAT_EDGE_MAX_DIM = _lib.DEFINES["DC_GAT_EDGE_MAX_DIM"]
 
 
 def gat_edge_fold(lin_edge_weight: torch.Tensor, att_edge: torch.Tensor) -> torch.Tensor:

@@ -18,8 +18,8 @@ from .sage import _sage_grad
 # blocks of the source row of h = x @ g.  The weights w [E, K] are formed once, in the order of the input edges (read
 # through the adjacency's ``perm``), and saved for the backward.  One launcher per C entry.
 # --------------------------------------------------------------------------- #
-GMM_MAX_K = 64        # DC_GMM_MAX_K in include/deformcontact.h
-GMM_MAX_D = 16        # DC_GMM_MAX_D
+GMM_MAX_K = _lib.DEFINES["DC_GMM_MAX_K"]
+GMM_MAX_D = _lib.DEFINES["DC_GMM_MAX_D"]
 GMM_REDUCES = ("mean", "add")
 
 

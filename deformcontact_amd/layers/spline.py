@@ -24,9 +24,9 @@ from .sage import _sage_grad
 # adjacency's ``perm``), and saved for the backward.  ``kernel_size``, ``is_open_spline`` and ``degree`` are host values
 # copied into the kernel arguments.  One launcher per C entry.
 # --------------------------------------------------------------------------- #
-SPLINE_MAX_D = 4       # DC_SPLINE_MAX_D in include/deformcontact.h
-SPLINE_MAX_S = 64      # DC_SPLINE_MAX_S
-SPLINE_MAX_K = 1024    # DC_SPLINE_MAX_K
+SPLINE_MAX_D = _lib.DEFINES["DC_SPLINE_MAX_D"]
+SPLINE_MAX_S = _lib.DEFINES["DC_SPLINE_MAX_S"]
+SPLINE_MAX_K = _lib.DEFINES["DC_SPLINE_MAX_K"]
 SPLINE_REDUCES = ("mean", "add")
 
 

@@ -45,12 +45,12 @@ from torch import Tensor
 from . import _lib
 from .graph import _require_cuda, current_stream_ptr
 
-#: the most neighbours one query keeps on this path (include/deformcontact.h DC_NEIGHBORS_MAX_CAP: a lane per rank)
-MAX_CAP = 64
-#: columns the width-F kernel stages per pass (include/deformcontact.h DC_NEIGHBORS_ND_CHUNK): widths below, at and
-#: above it and its multiples take different code paths, which is what the tests pick their widths by
-ND_CHUNK = 32
-_KNN, _RADIUS = 0, 1          # DC_NEIGHBORS_KNN / DC_NEIGHBORS_RADIUS
+#: the most neighbours one query keeps on this path (a lane per rank)
+MAX_CAP = _lib.DEFINES["DC_NEIGHBORS_MAX_CAP"]
+#: columns the width-F kernel stages per pass: widths below, at and above it and its multiples take different code
+#: paths, which is what the tests pick their widths by
+ND_CHUNK = _lib.DEFINES["DC_NEIGHBORS_ND_CHUNK"]
+_KNN, _RADIUS = _lib.DEFINES["DC_NEIGHBORS_KNN"], _lib.DEFINES["DC_NEIGHBORS_RADIUS"]
 _FLOWS = ("source_to_target", "target_to_source")
 
 

@@ -137,7 +137,7 @@ def propagate(g: GraphIndex, x: torch.Tensor, weighted: bool = True) -> torch.Te
     return _HopFn.apply(g, resolve(x), weighted)
 
 
-MAX_SEG = 4   # DC_MAX_SEG in include/deformcontact.h
+MAX_SEG = _lib.DEFINES["DC_MAX_SEG"]
 
 #: Direct parameter-gradient mode (opt-in, ``dp.GradBucket(params, direct=True)``): the dW
 #: slab-reduce kernel accumulates weight / bias gradients straight into the bucket's views instead

@@ -75,9 +75,9 @@ from . import _lib, neighbors
 from .deferred import resolve
 from .graph import _require_cuda, current_stream_ptr
 
-#: the most points of one graph that ``fps`` keeps in registers (include/deformcontact.h DC_FPS_RESIDENT_POINTS); a
-#: launch whose largest graph has more takes the workspace kernel
-FPS_RESIDENT_POINTS = 8192
+#: the most points of one graph that ``fps`` keeps in registers; a launch whose largest graph has more takes the
+#: workspace kernel
+FPS_RESIDENT_POINTS = _lib.DEFINES["DC_FPS_RESIDENT_POINTS"]
 
 
 def fps_count(n, ratio: float):

@@ -7,12 +7,16 @@
  * (`conv_layer(in, out)`, `conv(x, edge_index)`), whose arithmetic is PyG 2.5.2's
  * gcn_norm + MessagePassing.propagate + Linear.  Each entry point below names
  * the PyG/ATen step it replaces.  The Python host (deformcontact_amd/) binds
- * these with ctypes; INTEGRATION.md shows the binding.
+ * these with ctypes, deriving every signature and DC_* limit from the
+ * prototypes and #defines of this file ("Binding").
  *
  * Conventions
- *   - every pointer is a DEVICE pointer owned by the caller (PyTorch); the
- *     library allocates nothing and keeps no mutable global state except the
- *     thread-local last-error string;
+ *   - a pointer parameter is a DEVICE pointer owned by the caller (PyTorch)
+ *     unless it is marked DC_HOST (a host array the call reads, or writes,
+ *     before it returns), is a pointer to pointers (always a host array of
+ *     device pointers) or is a `char *` (host text); the library allocates
+ *     nothing and keeps no mutable global state except the thread-local
+ *     last-error string;
  *   - every call only ENQUEUES work on `stream` (a hipStream_t); no call
  *     synchronises, so all of them are legal inside hipGraph capture;
  *   - return value 0 = enqueued, <0 = DC_E* (nothing enqueued), message in
@@ -36,6 +40,7 @@ extern "C" {
 #define DC_EWORKSPACE (-3)
 
 typedef void *dc_stream_t; /* hipStream_t */
+#define DC_HOST            /* marks a single-star pointer parameter that points to HOST memory (see Conventions) */
 
 #define DC_MAX_PARTS 4     /* edge_index parts of one merged (block-diagonal) adjacency */
 #define DC_MAX_GROUPS 4    /* row groups with their own weights in one grouped dense launch */
@@ -113,8 +118,8 @@ int dc_graph_build(const int64_t *edge_index, int64_t E, int64_t N, int self_loo
  * of part p come out exactly as dc_graph_build over that part alone would emit them (same stable
  * order, same gcn_norm weights), with `other` shifted by the part's offset and `perm` by the
  * part's first edge id. */
-int dc_graph_build_parts(const int64_t *const *edge_index_parts, const int64_t *E_parts,
-                         const int64_t *node_offset_parts, const int64_t *nodes_parts, int nparts,
+int dc_graph_build_parts(const int64_t *const *edge_index_parts, DC_HOST const int64_t *E_parts,
+                         DC_HOST const int64_t *node_offset_parts, DC_HOST const int64_t *nodes_parts, int nparts,
                          int64_t N, int self_loops,
                          int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
                          int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
@@ -126,7 +131,7 @@ int dc_graph_build_parts(const int64_t *const *edge_index_parts, const int64_t *
  * DC_CSR_BUCKETS_MIN slots (env, default 2^19; slots = E, + N with self loops), buckets such that an average
  * bucket fills at most a quarter of one 12,288-slot LDS pass, at most 2,048 nodes per bucket and 8,192 buckets.
  * (Diagnostic / test hook: nothing in the reference corresponds to it.) */
-int dc_graph_build_plan(int64_t E, int64_t N, int self_loops, int *bucket_shift, int *buckets);
+int dc_graph_build_plan(int64_t E, int64_t N, int self_loops, DC_HOST int *bucket_shift, DC_HOST int *buckets);
 
 /* dc_graph_build for a BATCH of graphs whose layout is known (Batch.from_data_list, the loaders of
  * /root/reference/loaders/everyday.py:96 via torch_geometric.data.Batch): graph i owns nodes
@@ -142,7 +147,7 @@ int dc_graph_build_plan(int64_t E, int64_t N, int self_loops, int *bucket_shift,
 #define DC_SEG_MAX_NODES 4096
 #define DC_SEG_MAX_EDGES 16384
 int dc_graph_build_segmented(const int64_t *edge_index, int64_t E, int64_t N,
-                             const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                             DC_HOST const int64_t *node_ptr_host, DC_HOST const int64_t *edge_ptr_host, int nseg,
                              int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
                              int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
                              int32_t *status, dc_stream_t stream);
@@ -157,7 +162,7 @@ int dc_graph_build_segmented(const int64_t *edge_index, int64_t E, int64_t N,
  * build flags sits on its graph's node 0 in the image as in `other`). */
 int64_t dc_hop_chain_image_bytes(int64_t N);
 int dc_graph_build_segmented_image(const int64_t *edge_index, int64_t E, int64_t N,
-                                   const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                                   DC_HOST const int64_t *node_ptr_host, DC_HOST const int64_t *edge_ptr_host, int nseg,
                                    int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
                                    int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
                                    void *image_f, void *image_b, int32_t *status, dc_stream_t stream);
@@ -169,7 +174,7 @@ int dc_graph_build_segmented_image(const int64_t *edge_index, int64_t E, int64_t
  * graph's first node; a self loop outside its graph's node range is flagged and dropped.  The count costs a read of
  * nseg * E / 2 edges per side: meant for small batches. */
 int dc_graph_build_segmented_loops(const int64_t *edge_index, int64_t E, int64_t N,
-                                   const int64_t *node_ptr_host, const int64_t *edge_ptr_host, int nseg,
+                                   DC_HOST const int64_t *node_ptr_host, DC_HOST const int64_t *edge_ptr_host, int nseg,
                                    int32_t *ptr_f, int32_t *other_f, int32_t *perm_f, float *w_f,
                                    int32_t *ptr_b, int32_t *other_b, int32_t *perm_b, float *w_b,
                                    int32_t *status, dc_stream_t stream);
@@ -178,8 +183,8 @@ int dc_graph_build_segmented_loops(const int64_t *edge_index, int64_t E, int64_t
  * axis is mapped from [lo[a], lo[a] + 1 / inv_extent[a]) to 10 bits (lo / inv_extent are HOST
  * arrays of 3 floats).  The host sorts nodes by it (graph.NodeOrder.morton) so that the rows a
  * radius-graph hop gathers (utils/pointcloud_utils.py:10) are neighbours in memory. */
-int dc_morton_codes(const float *pos, int64_t ld, int64_t n, const float *lo_host,
-                    const float *inv_extent_host, int64_t *codes, dc_stream_t stream);
+int dc_morton_codes(const float *pos, int64_t ld, int64_t n, DC_HOST const float *lo_host,
+                    DC_HOST const float *inv_extent_host, int64_t *codes, dc_stream_t stream);
 
 /* ---- node reordering of one big graph, on the device (dc_order.hip; BASELINE.json configs[4]) ----
  * dc_morton_order: Z-order permutation of a point cloud pos [n, >= 3] (fp32, leading dimension ld): the bounding
@@ -344,7 +349,7 @@ int64_t dc_hop_chain_max_nodes(void);
  * in 0.3 - 1.75 % of two-stream train steps; profiles/r05/README.md). */
 int64_t dc_hop_chain_lds_request(void);
 int dc_hop_chain_f32(const int32_t *ptr, const int32_t *other, const float *w, const int32_t *deg_ptr,
-                     int64_t cap, const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
+                     int64_t cap, DC_HOST const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
                      int64_t F, int K, int src_block, int dir, float *rowmax, int mode,
                      dc_stream_t stream);
 /* dc_hop_chain_f32 with the table image of the set it walks (image_f of dc_graph_build_segmented_image for the
@@ -352,7 +357,7 @@ int dc_hop_chain_f32(const int32_t *ptr, const int32_t *other, const float *w, c
  * its graph's tables from the image instead of building them from ptr / other / deg_ptr; same blocks and row maxima,
  * bit for bit.  image == NULL, or a launch that does not take the LDS-table form: exactly dc_hop_chain_f32. */
 int dc_hop_chain_image_f32(const int32_t *ptr, const int32_t *other, const float *w, const int32_t *deg_ptr,
-                           int64_t cap, const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
+                           int64_t cap, DC_HOST const int64_t *node_ptr_host, int nseg, float *slab, int64_t ld, int64_t N,
                            int64_t F, int K, int src_block, int dir, float *rowmax, int mode, const void *image,
                            dc_stream_t stream);
 
@@ -412,7 +417,7 @@ int dc_contact_loss(const int32_t *ptr_f, const int32_t *other_f, const int32_t 
  * [Fo,Fi] (ld = Fi).  Exact fp32 (v_mfma_f32_32x32x2_f32 is an fmaf chain).
  */
 #define DC_MAX_SEG 4
-int dc_tag_linear_fwd(const float *const *xs, const int64_t *ldxs, const float *const *ws,
+int dc_tag_linear_fwd(const float *const *xs, DC_HOST const int64_t *ldxs, const float *const *ws,
                       int nseg, const float *bias, int relu, float *out, int64_t ldo,
                       int64_t N, int64_t Fi, int64_t Fo, dc_stream_t stream);
 
@@ -421,7 +426,7 @@ int dc_tag_linear_fwd(const float *const *xs, const int64_t *ldxs, const float *
  * g is taken as 0 where out <= 0; NULL = no mask). */
 int dc_tag_linear_bwd_dx(const float *g, int64_t ldg, const float *out_for_mask, int64_t ldo,
                          const float *const *ws, int nseg, float *const *gxs,
-                         const int64_t *ldgxs, int64_t N, int64_t Fi, int64_t Fo,
+                         DC_HOST const int64_t *ldgxs, int64_t N, int64_t Fi, int64_t Fo,
                          dc_stream_t stream);
 
 /* Variants on the bf16 matrix cores.  Every fp32 operand is split exactly into bf16 terms
@@ -435,7 +440,7 @@ int dc_tag_linear_bwd_dx(const float *g, int64_t ldg, const float *out_for_mask,
  * Same arguments and semantics as the functions above; shapes the split kernels do not cover
  * (unaligned operands, reduction extent not a multiple of 16) silently take the fp32 path.
  * The dX variant needs a scratch of ..._workspace_bytes() for transposed weights. */
-int dc_tag_linear_fwd_split(const float *const *xs, const int64_t *ldxs, const float *const *ws,
+int dc_tag_linear_fwd_split(const float *const *xs, DC_HOST const int64_t *ldxs, const float *const *ws,
                             int nseg, const float *bias, int relu, float *out, int64_t ldo,
                             int64_t N, int64_t Fi, int64_t Fo, int products, dc_stream_t stream);
 /* The forward dense block of a TAGConv layer with a SHORT reduction - the first layer of each encoder branch
@@ -462,7 +467,7 @@ int dc_tag_linear_fwd_narrow_img(const float *slab, int64_t ld, const void *wimg
 int64_t dc_tag_linear_bwd_dx_split_workspace_bytes(int64_t Fi, int64_t Fo, int nseg);
 int dc_tag_linear_bwd_dx_split(const float *g, int64_t ldg, const float *out_for_mask,
                                int64_t ldo, const float *const *ws, int nseg, float *const *gxs,
-                               const int64_t *ldgxs, void *workspace, int64_t workspace_bytes,
+                               DC_HOST const int64_t *ldgxs, void *workspace, int64_t workspace_bytes,
                                int64_t N, int64_t Fi, int64_t Fo, int products, dc_stream_t stream);
 
 /* dW-side: (g*relu')^T[Fo,N] . xs[s][N,Fi] (same optional ReLU mask), gbias[Fo] = column
@@ -477,13 +482,13 @@ int dc_tag_linear_bwd_dx_split(const float *g, int64_t ldg, const float *out_for
  * atomics). */
 int64_t dc_tag_linear_bwd_dw_workspace_bytes(int64_t N, int64_t Fi, int64_t Fo, int nseg);
 int dc_tag_linear_bwd_dw(const float *g, int64_t ldg, const float *out_for_mask, int64_t ldo,
-                         const float *const *xs, const int64_t *ldxs, int nseg,
+                         const float *const *xs, DC_HOST const int64_t *ldxs, int nseg,
                          float *const *gws, int ngw, int64_t gw_cols, float *gbias,
                          int accumulate, void *partials, int64_t partials_bytes, int64_t N,
                          int64_t Fi, int64_t Fo, dc_stream_t stream);
 /* split-bf16x6 variant of the above (operands read through ds_read_b64_tr_b16) */
 int dc_tag_linear_bwd_dw_split(const float *g, int64_t ldg, const float *out_for_mask,
-                               int64_t ldo, const float *const *xs, const int64_t *ldxs, int nseg,
+                               int64_t ldo, const float *const *xs, DC_HOST const int64_t *ldxs, int nseg,
                                float *const *gws, int ngw, int64_t gw_cols, float *gbias,
                                int accumulate, void *partials, int64_t partials_bytes, int64_t N,
                                int64_t Fi, int64_t Fo, int products, dc_stream_t stream);
@@ -502,17 +507,17 @@ int dc_tag_linear_bwd_dw_split(const float *g, int64_t ldg, const float *out_for
  * Any upper bound is a valid reference.  fp16 denormals are honoured by the matrix core: elements
  * down to 2^-39 of their reference keep absolute accuracy.  Shapes: Fi % 16 == 0 (forward),
  * Fo % 16 == 0 (dX), N % 16 == 0 (dW), 16-byte aligned rows; otherwise DC_EINVAL (use *_split). */
-int dc_tag_linear_fwd_h2(const float *const *xs, const int64_t *ldxs, const float *const *ws,
+int dc_tag_linear_fwd_h2(const float *const *xs, DC_HOST const int64_t *ldxs, const float *const *ws,
                          int nseg, const float *bias, int relu, float *out, int64_t ldo, int64_t N,
                          int64_t Fi, int64_t Fo, const float *x_rowmax, const float *w_rowmax,
                          dc_stream_t stream);
 int dc_tag_linear_bwd_dx_h2(const float *g, int64_t ldg, const float *out_for_mask, int64_t ldo,
                             const float *const *ws, int nseg, float *const *gxs,
-                            const int64_t *ldgxs, void *workspace, int64_t workspace_bytes,
+                            DC_HOST const int64_t *ldgxs, void *workspace, int64_t workspace_bytes,
                             int64_t N, int64_t Fi, int64_t Fo, const float *g_rowmax,
                             const float *w_rowmax, dc_stream_t stream);
 int dc_tag_linear_bwd_dw_h2(const float *g, int64_t ldg, const float *out_for_mask, int64_t ldo,
-                            const float *const *xs, const int64_t *ldxs, int nseg,
+                            const float *const *xs, DC_HOST const int64_t *ldxs, int nseg,
                             float *const *gws, int ngw, int64_t gw_cols, float *gbias,
                             int accumulate, void *partials, int64_t partials_bytes, int64_t N,
                             int64_t Fi, int64_t Fo, const float *g_rowmax, const float *x_rowmax,
@@ -521,7 +526,7 @@ int dc_tag_linear_bwd_dw_h2(const float *g, int64_t ldg, const float *out_for_ma
  * time (g2 with g's leading dimension): the attention backward's dK = (dS' - eps o P)^T Q without materialising the
  * corrected dS.  128 x 256 tile kernel only: Fo % 128 == 0, Fi == 256 per segment, N % 32 == 0. */
 int dc_tag_linear_bwd_dw_h2_corr(const float *g, int64_t ldg, const float *g2, const float *g2_coef,
-                                 const float *const *xs, const int64_t *ldxs, int nseg, float *const *gws, int ngw,
+                                 const float *const *xs, DC_HOST const int64_t *ldxs, int nseg, float *const *gws, int ngw,
                                  int64_t gw_cols, int accumulate, void *partials, int64_t partials_bytes, int64_t N,
                                  int64_t Fi, int64_t Fo, const float *g_rowmax, const float *x_rowmax,
                                  dc_stream_t stream);
@@ -601,19 +606,20 @@ int dc_tag_linear_fwd_h2p_corr(const float *x, int64_t ldx, const float *x2, con
 int dc_tag_grouped_weight_prep(const float *const *ws, int ngroups, int nseg, int64_t Fo, int64_t Fi,
                                float *const *w_rowmax, void *const *w_image, void *const *wt_image,
                                float *const *wt_rowmax, dc_stream_t stream);
-int dc_tag_grouped_fwd_h2p(const float *x, int64_t ldx, int ngroups, const int64_t *row_beg,
-                           const int64_t *rows, int64_t N_total, const void *const *w_images,
+int dc_tag_grouped_fwd_h2p(const float *x, int64_t ldx, int ngroups, DC_HOST const int64_t *row_beg,
+                           DC_HOST const int64_t *rows, int64_t N_total, const void *const *w_images,
                            const float *const *biases, int relu, float *out, int64_t ldo, int64_t K,
                            int64_t Fo, const float *x_rowmax, const float *const *w_rowmaxes,
                            dc_stream_t stream);
-int dc_tag_grouped_mask_grad(const float *const *g, const int64_t *ldg, int ngroups, const int64_t *row_beg,
-                             const int64_t *rows, int64_t N_total, const float *out_for_mask, int64_t ldo,
+int dc_tag_grouped_mask_grad(const float *const *g, DC_HOST const int64_t *ldg, int ngroups,
+                             DC_HOST const int64_t *row_beg, DC_HOST const int64_t *rows, int64_t N_total,
+                             const float *out_for_mask, int64_t ldo,
                              float *gm, int64_t ldgm, int64_t F, float *rowmax_a, float *rowmax_b,
                              dc_stream_t stream);
-int64_t dc_tag_grouped_bwd_dw_workspace_bytes(const int64_t *rows, int ngroups, int64_t Fi, int64_t Fo,
+int64_t dc_tag_grouped_bwd_dw_workspace_bytes(DC_HOST const int64_t *rows, int ngroups, int64_t Fi, int64_t Fo,
                                               int nseg);
-int dc_tag_grouped_bwd_dw_h2(const float *g, int64_t ldg, const float *const *xs, const int64_t *ldxs,
-                             int nseg, int ngroups, const int64_t *row_beg, const int64_t *rows,
+int dc_tag_grouped_bwd_dw_h2(const float *g, int64_t ldg, const float *const *xs, DC_HOST const int64_t *ldxs,
+                             int nseg, int ngroups, DC_HOST const int64_t *row_beg, DC_HOST const int64_t *rows,
                              int64_t N_total, float *const *gws, float *const *gbias, int accumulate,
                              void *partials, int64_t partials_bytes, int64_t Fi, int64_t Fo,
                              const float *g_rowmax, const float *x_rowmax, dc_stream_t stream);
@@ -1080,8 +1086,8 @@ int dc_gmm_bwd_params(const float *gw, const float *w, const float *a, int64_t l
 #define DC_SPLINE_MAX_D 4
 #define DC_SPLINE_MAX_S 64
 #define DC_SPLINE_MAX_K 1024
-int dc_spline_basis(const float *a, int64_t lda, const int64_t *ks, const int32_t *open, int64_t degree, float *b,
-                    int32_t *wi, int64_t E, int64_t D, dc_stream_t stream);
+int dc_spline_basis(const float *a, int64_t lda, DC_HOST const int64_t *ks, DC_HOST const int32_t *open,
+                    int64_t degree, float *b, int32_t *wi, int64_t E, int64_t D, dc_stream_t stream);
 int dc_spline_fwd(const int32_t *ptr, const int32_t *other, const int32_t *perm, const float *b, const int32_t *wi,
                   const float *h, int64_t ldh, const float *base, int64_t ldb, int mean, int relu, float *y,
                   int64_t ldy, int64_t N, int64_t E, int64_t S, int64_t K, int64_t M, dc_stream_t stream);
@@ -1091,7 +1097,7 @@ int dc_spline_bwd_h(const int32_t *ptr_t, const int32_t *other_t, const int32_t 
 int dc_spline_bwd_b(const int64_t *src, const int64_t *dst, const int32_t *ptr, const int32_t *wi, const float *h,
                     int64_t ldh, const float *gy, int64_t ldgy, float *gb, int64_t N, int64_t E, int64_t S, int64_t K,
                     int64_t M, dc_stream_t stream);
-int dc_spline_bwd_a(const float *gb, const float *a, int64_t lda, const int64_t *ks, const int32_t *open,
+int dc_spline_bwd_a(const float *gb, const float *a, int64_t lda, DC_HOST const int64_t *ks, DC_HOST const int32_t *open,
                     int64_t degree, float *ga, int64_t ldga, int64_t E, int64_t D, dc_stream_t stream);
 
 /* ---- Point-set sampling and transfer (dc_pointops.hip; PyG fps, knn_interpolate) ----

@@ -505,7 +505,10 @@ int dc_tag_linear_bwd_dw_split(const float *g, int64_t ldg, const float *out_for
  *   dW      : the contraction runs over nodes, so g * relu' and x get ONE scale per node chunk of
  *             the split-N plan: the maxima of g_rowmax / x_rowmax over the chunk (inside the kernel).
  * Any upper bound is a valid reference.  fp16 denormals are honoured by the matrix core: elements
- * down to 2^-39 of their reference keep absolute accuracy.  Shapes: Fi % 16 == 0 (forward),
+ * down to 2^-39 of their reference keep absolute accuracy.  The shared-scale entries (dX: the
+ * weights, dW: a node chunk) are therefore fp32-accurate only while rows that meet in one reduction
+ * spread over at most 2^22 against each other (gradient rows falling while activation rows rise;
+ * table in DESIGN.md 4.3).  Shapes: Fi % 16 == 0 (forward),
  * Fo % 16 == 0 (dX), N % 16 == 0 (dW), 16-byte aligned rows; otherwise DC_EINVAL (use *_split). */
 int dc_tag_linear_fwd_h2(const float *const *xs, DC_HOST const int64_t *ldxs, const float *const *ws,
                          int nseg, const float *bias, int relu, float *out, int64_t ldo, int64_t N,

@@ -38,6 +38,47 @@ def row_rel_err(a, b):
     return float((np.abs(a - b).max(axis=1) / scale).max())
 
 
+def col_rel_err(a, b):
+    """``row_rel_err`` over the columns: each column of a 2-D result on its own scale."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    assert a.ndim == 2 and a.shape == b.shape, (a.shape, b.shape)
+    return row_rel_err(a.T, b.T)
+
+
+def cw_err(got, exact, S):
+    """Component-wise distance max |got - exact| / S, where ``S`` is the sum of the absolute values of the terms
+    ``exact`` sums (tests/h2_model.py).  A component with S = 0 sums only zeros: it must be exactly 0 in ``got``."""
+    got, exact, S = (np.asarray(v, dtype=np.float64) for v in (got, exact, S))
+    assert got.shape == exact.shape == S.shape, (got.shape, exact.shape, S.shape)
+    zero = S == 0
+    assert not got[zero].any(), "a component whose terms are all zero is not exactly 0"
+    if zero.all():
+        return 0.0
+    return float((np.abs(got - exact)[~zero] / S[~zero]).max())
+
+
+def h2_parity_operands(n, fi, fo, nseg, regime):
+    """(slab [N, nseg * Fi], g [N, Fo], [W_s [Fo, Fi]], bias [Fo]) in fp32: the operands of
+    tests/test_gpu_parity.py::test_dense_block_fp16x2_vs_float64 - one generator for that test and for the CPU test that
+    proves which of its metrics the arithmetic's model supports (tests/test_h2_model.py)."""
+    from oracle.weights import hashed_uniform
+    slab, g = hashed_uniform((n, nseg * fi), 5, 2.0), hashed_uniform((n, fo), 91, 2.0)
+    wscale = 2.0 / np.sqrt(fi)
+    if regime == "wide_rows":                                    # node rows over 1e6, g against x
+        rs = np.logspace(-6, 0, n, dtype=np.float32)[:, None]
+        slab, g = slab * rs, g * rs[::-1]
+    elif regime == "tiny":
+        slab, g, wscale = slab * np.float32(1e-12), g * np.float32(1e-12), wscale * 1e-6
+    elif regime == "huge":
+        slab, g, wscale = slab * np.float32(1e12), g * np.float32(1e10), wscale * 1e3
+    else:
+        assert regime == "unit", regime
+    slab, g = np.ascontiguousarray(slab, np.float32), np.ascontiguousarray(g, np.float32)
+    ws = [hashed_uniform((fo, fi), 40 + s, wscale) for s in range(nseg)]
+    bias = (hashed_uniform((fo,), 77, 0.5) * np.float32(np.abs(slab).max()) * np.float32(wscale)).astype(np.float32)
+    return slab, g, ws, bias
+
+
 #: every parity comparison of a test run: (test id, tensor, HIP-vs-fp32-oracle distance, did the float64 widening fire,
 #: HIP-vs-float64, oracle-vs-float64) - tests/conftest.py writes it to gpurun_out/parity_distances.json at session end
 #: (VERDICT r03: "nothing records how often the widening fires or the worst HIP-vs-fp32-oracle distance")

@@ -11,8 +11,8 @@ from deformcontact_amd import ops
 from deformcontact_amd.graph import GraphIndex, clear_cache
 from oracle import hop_c, pyg_ref
 from oracle.weights import fill_state_dict_, hashed_uniform
-from tests.helpers import (G, record_parity, assert_parity, golden_graphs, load_golden, random_multigraph, rel_err,
-                           row_rel_err)
+from tests.helpers import (G, record_parity, assert_parity, col_rel_err, golden_graphs, h2_parity_operands, load_golden,
+                           random_multigraph, rel_err, row_rel_err)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -426,21 +426,11 @@ def test_dense_block_fp16x2_vs_float64(n, fi, fo, nseg, relu, regime):
     from deformcontact_amd.ops import _i64_array, _ptr_array
     L = _lib.lib()
     st = current_stream_ptr(torch.device(DEV))
-    slab = torch.from_numpy(hashed_uniform((n, nseg * fi), 5, 2.0)).to(DEV)
-    g = torch.from_numpy(hashed_uniform((n, fo), 91, 2.0)).to(DEV)
-    wscale = 2.0 / np.sqrt(fi)
-    if regime == "wide_rows":
-        rs = torch.logspace(-6, 0, n, device=DEV).unsqueeze(1)
-        slab, g = slab * rs, g * rs.flip(0)
-    elif regime == "tiny":
-        slab, g, wscale = slab * 1e-12, g * 1e-12, wscale * 1e-6
-    elif regime == "huge":
-        slab, g, wscale = slab * 1e12, g * 1e10, wscale * 1e3
-    slab, g = slab.contiguous(), g.contiguous()
+    slab, g, ws, bias = h2_parity_operands(n, fi, fo, nseg, regime)
+    slab, g, bias = (torch.from_numpy(t).to(DEV) for t in (slab, g, bias))
     xs = [slab[:, s * fi:(s + 1) * fi] for s in range(nseg)]
     ld = [nseg * fi] * nseg
-    ws = [torch.from_numpy(hashed_uniform((fo, fi), 40 + s, wscale)).to(DEV) for s in range(nseg)]
-    bias = torch.from_numpy(hashed_uniform((fo,), 77, 0.5)).to(DEV) * float(slab.abs().max()) * wscale
+    ws = [torch.from_numpy(w).to(DEV) for w in ws]
     rowmax = slab.abs().amax(1).contiguous()
     ref = sum(xs[s].double().cpu() @ ws[s].double().cpu().t() for s in range(nseg)) + bias.double().cpu()
     if relu:
@@ -522,7 +512,15 @@ def test_dense_block_fp16x2_vs_float64(n, fi, fo, nseg, relu, regime):
                                          _ptr_array(gws), nseg, fi, gb.data_ptr(), 0, scratch.data_ptr(),
                                          nbytes, n, fi, fo, growmax.data_ptr(), rowmax.data_ptr(), st), "dw_h2")
     for s in range(nseg):
-        assert rel_err(_np(gws[s]), (gm.t() @ xs[s].double().cpu()).numpy()) < 2e-6, s
+        gw_ref = (gm.t() @ xs[s].double().cpu()).numpy()
+        assert rel_err(_np(gws[s]), gw_ref) < 2e-6, s
+        # per input column and per output row as well, wherever the arithmetic's exact model alone is within 1e-6 of
+        # float64 (tests/test_h2_model.py::test_parity_dw_regimes_are_conditioned): everywhere but the rows of "wide_rows"
+        # at 144 x 32 x 48 - 144 nodes spread over 1e6 against each other under ONE scale put the model itself at 2.9e-6
+        # on the worst row there, the design's envelope, which the kernel reproduces (2.8e-6)
+        assert col_rel_err(_np(gws[s]), gw_ref) < 2e-6, s
+        if (regime, n) != ("wide_rows", 144):
+            assert row_rel_err(_np(gws[s]), gw_ref) < 2e-6, s
     assert rel_err(_np(gb), gm.sum(0).numpy()) < 2e-6
 
 

@@ -134,8 +134,14 @@ for n, nseg in ((4096, 4), (2080, 1), (8192 + 32, 3)):
     torch.cuda.synchronize()
     for s in range(nseg):
         ref = g.double().cpu().t() @ xs[s].double().cpu()
-        err = float((gws[s].double().cpu() - ref).abs().max() / ref.abs().max())
+        got = gws[s].double().cpu()
+        err = float((got - ref).abs().max() / ref.abs().max())
         assert err < 2e-6, (err, n, s)
+        # each output row and each column on its own scale (the exact model of the arithmetic alone is within 1e-6 of
+        # float64 on both here: tests/test_h2_model.py::test_wide_dw_regime_is_conditioned)
+        err_row = float(((got - ref).abs().amax(1) / ref.abs().amax(1)).max())
+        err_col = float(((got - ref).abs().amax(0) / ref.abs().amax(0)).max())
+        assert err_row < 2e-6 and err_col < 2e-6, (err_row, err_col, n, s)
         worst = max(worst, err)
         digest.update(gws[s].cpu().numpy().tobytes())
     refb = g.double().cpu().sum(0)

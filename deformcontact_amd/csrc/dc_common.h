@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/deformcontact.h"
 
@@ -39,6 +40,17 @@ inline void trace_site(const Site *site, const char *name) {
 }
 
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// An environment switch: its integer value, `dflt` when unset or empty.  The ONE reader of the environment in csrc/ (but
+// for dc_core.hip's PYTEST_CURRENT_TEST).  Two read times, chosen at the call site: a switch that tests flip inside one
+// process (DC_CSR_BUCKETS*, DC_CSR_BUCKET_SHIFT, DC_DW_BF16_DMA) is read on every call; one that only chooses between
+// kernels for a whole process (DC_H2_*, DC_DW_WIDE, DC_DENSE_TRACE; tests set those through child processes) is read
+// once, into a function-local `static const int`.
+inline int64_t env_int64(const char *name, int64_t dflt) {
+    const char *v = getenv(name);
+    return (v && *v) ? atoll(v) : dflt;
+}
+inline int env_int(const char *name, int dflt) { return (int)env_int64(name, dflt); }
 
 inline int check_launch(const char *what) {
     hipError_t e = hipGetLastError();

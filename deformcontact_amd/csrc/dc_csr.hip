@@ -997,15 +997,19 @@ k_bk_weights(Build b) {
 
 static inline int64_t align16(int64_t b) { return (b + 15) & ~int64_t(15); }
 
+// Forced off / forced on / threshold, decided HERE for the sizing of the workspace (may_bucket) and for the build
+// (bucket_plan), which must agree: DC_CSR_BUCKETS = 0 / 1 forces the choice, otherwise DC_CSR_BUCKETS_MIN slots
+// (default 2^19) are the threshold.  Read at every call (tests change them inside one process).
+static bool bucket_wanted(int64_t slots) {
+    const int mode = env_int("DC_CSR_BUCKETS", -1);
+    if (mode == 0 || mode == 1) return mode == 1;
+    return slots >= env_int64("DC_CSR_BUCKETS_MIN", (int64_t)1 << 19);
+}
+
 // Can a build over E edges and N nodes take the bucketed path (bucket_plan below)?  Its slots are E, or E + N with self
 // loops - the workspace entries do not know which, so E + N decides.  Mesh batches (the reference's configurations) stay
 // far below the threshold and do not pay for the bucket arrays (~10 B x (E + N) + 64 KiB per side).
-static bool may_bucket(int64_t E, int64_t N) {
-    const char *mode = getenv("DC_CSR_BUCKETS"), *min_s = getenv("DC_CSR_BUCKETS_MIN");
-    if (mode && atoi(mode) == 0) return false;
-    if (mode && atoi(mode) == 1) return true;
-    return E + N >= (min_s ? atoll(min_s) : (int64_t)1 << 19);
-}
+static bool may_bucket(int64_t E, int64_t N) { return bucket_wanted(E + N); }
 
 static inline int64_t side_bytes(int64_t E, int64_t N) {
     const int64_t ntiles = (N + kScanTile - 1) / kScanTile;
@@ -1052,13 +1056,11 @@ static char *carve_side(Side &sd, char *ws, int64_t E, int64_t N) {
 // cloud hold several times the average; 100k-point graph: 256 nodes, 154 us against 169 us with 512).  DC_CSR_BUCKETS = 0 / 1 forces the
 // choice, DC_CSR_BUCKET_SHIFT the bucket size (tests: multi-pass buckets and single-node passes at small sizes).
 static bool bucket_plan(int64_t slots, int64_t N, Buckets &bk) {
-    const char *mode = getenv("DC_CSR_BUCKETS"), *min_s = getenv("DC_CSR_BUCKETS_MIN"), *sh = getenv("DC_CSR_BUCKET_SHIFT");
-    if (mode && atoi(mode) == 0) return false;
-    const int64_t min_slots = min_s ? atoll(min_s) : (int64_t)1 << 19;
-    if (!(mode && atoi(mode) == 1) && slots < min_slots) return false;
+    if (!bucket_wanted(slots)) return false;
+    const int sh = env_int("DC_CSR_BUCKET_SHIFT", -1);
     int s = 4;
     while (s < kBkMaxShift && ((int64_t)2 << s) * slots <= (int64_t)(kBkEdges / 4) * N) ++s;
-    if (sh) s = atoi(sh) < 1 ? 1 : (atoi(sh) > kBkMaxShift ? kBkMaxShift : atoi(sh));
+    if (sh >= 0) s = sh < 1 ? 1 : (sh > kBkMaxShift ? kBkMaxShift : sh);
     while (s < kBkMaxShift && ((N + ((int64_t)1 << s) - 1) >> s) > kBkMaxBuckets) ++s;
     const int64_t nb = (N + ((int64_t)1 << s) - 1) >> s;
     if (nb > kBkMaxBuckets) return false;

@@ -61,12 +61,7 @@ __device__ __forceinline__ bf16x8 tr_operand(const char *plane, int m0) {
     return tr_read<ROWB>(plane + (8 * h + q) * ROWB + (m0 + 16 * (g & 1) + 4 * pp) * 2);
 }
 
-// host side of the launchers (al16: dc_common.h)
-inline int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
+// host side of the launchers (al16, env_int: dc_common.h)
 struct Mat {
     const float *p;
     int64_t ld;

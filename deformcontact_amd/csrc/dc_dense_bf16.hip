@@ -683,9 +683,9 @@ bool dw_bf16_launch(const DwBf16Params &p, hipStream_t hs) {
     if (grid >= (int64_t)INT32_MAX) return false;
     // both operands by LDS-DMA when a chunk's byte offsets fit the buffer instructions' 32 bits (DC_DW_BF16_DMA=0: the
     // register-staged kernel; bit-identical partials)
-    const char *dma = getenv("DC_DW_BF16_DMA");
+    const bool dma = env_int("DC_DW_BF16_DMA", 1) != 0;          // (per call: tests flip it inside one process)
     const int64_t span = (p.chunk_rows + kDwbK) * (p.ldg > p.ldx ? p.ldg : p.ldx) * 2;
-    if (!(dma && atoi(dma) == 0) && span < ((int64_t)1 << 31)) {
+    if (dma && span < ((int64_t)1 << 31)) {
         DC_LAUNCH(k_dw_bf16d, dim3((unsigned)grid), dim3(768), 0, hs, p);
         return true;
     }
@@ -714,11 +714,10 @@ extern "C" int dc_tag_linear_fwd_bf16(const uint16_t *a, int64_t lda, const uint
                "dc_tag_linear_fwd_bf16: leading dimension too large for 32-bit tile offsets");
     Bf16Params p{a, w, bias, out, lda, ldo, N, K, Fo, relu, out_is_bf16};
     // 256 x 256 tiles (one per CU) once a launch has enough of them to fill most of the chip and K is whole 64-deep
-    // tiles; else the 128 x 128 kernel.  DC_BF16_X=0 / 1 forces the choice (experiments; results are bit-identical).
-    static const int force = getenv("DC_BF16_X") ? atoi(getenv("DC_BF16_X")) : -1;
+    // tiles; else the 128 x 128 kernel (results are bit-identical).
     const int64_t xtiles = ((N + kGxBM - 1) / kGxBM) * ((Fo + kGxBN - 1) / kGxBN);
     const bool xok = K % kGxBK == 0 && lda * kGxBM < ((int64_t)1 << 31) && K * kGxBN < ((int64_t)1 << 31);
-    if (xok && (force == 1 || (force != 0 && xtiles >= 160))) {
+    if (xok && xtiles >= 160) {
         if (out_is_bf16) DC_LAUNCH(k_fwd_bf16x<true>, dim3((unsigned)xtiles), dim3(512), 0, stream, p);
         else DC_LAUNCH(k_fwd_bf16x<false>, dim3((unsigned)xtiles), dim3(512), 0, stream, p);
         return check_launch("dc_tag_linear_fwd_bf16");

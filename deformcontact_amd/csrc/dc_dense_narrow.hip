@@ -29,13 +29,6 @@
 #include "dc_dense.h"
 #include "dc_narrow_image.h"
 
-// timing-only ablations (tools/r06/narrow_abl.sh builds this file with -DDC_NARROW_ABL=<bits>; results are wrong by
-// construction): 1 no MFMAs, 2 no weight image (fragments made up), 4 no row stores, 8 no row loads / plane image, 16 no
-// accumulator staging
-#ifndef DC_NARROW_ABL
-#define DC_NARROW_ABL 0
-#endif
-
 namespace dc {
 
 struct NarrowParams {
@@ -77,14 +70,14 @@ __device__ __forceinline__ void narrow_self_weights(const NarrowParams &p, char 
 #pragma unroll
             for (int j = 0; j < MAXQ; ++j) {
                 const int q = (int)threadIdx.x + 256 * j;
-                if (!(DC_NARROW_ABL & 2) && s < p.nseg && q < per4) wv[s][j] = *reinterpret_cast<const f32x4 *>(p.w[s] + 4 * q);
+                if (s < p.nseg && q < per4) wv[s][j] = *reinterpret_cast<const f32x4 *>(p.w[s] + 4 * q);
             }
 #pragma unroll
         for (int s = 0; s < kMaxSeg; ++s)
 #pragma unroll
             for (int j = 0; j < MAXQ; ++j) {
                 const int q = (int)threadIdx.x + 256 * j;
-                if (!(DC_NARROW_ABL & 2) && s < p.nseg && q < per4) {
+                if (s < p.nseg && q < per4) {
                     int o = (4 * q) / p.fi, f = 4 * q - o * p.fi;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -154,8 +147,7 @@ __device__ __forceinline__ void narrow_block(const NarrowParams &p, const bf16x8
             const int r = q / PPR, c4 = q - r * PPR;
             int64_t row = row0 + r;
             row = row < p.N ? row : p.N - 1;
-            if (DC_NARROW_ABL & 8) xv[j] = f32x4{(float)row, 1.f, 2.f, 3.f};
-            else xv[j] = *reinterpret_cast<const f32x4 *>(p.x + row * p.ld + 4 * c4);
+            xv[j] = *reinterpret_cast<const f32x4 *>(p.x + row * p.ld + 4 * c4);
         }
     };
     int t = blockIdx.x;
@@ -171,12 +163,7 @@ __device__ __forceinline__ void narrow_block(const NarrowParams &p, const bf16x8
             for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) {
-                    if (DC_NARROW_ABL & 2) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) fb[nb][ks][pl][j] = (__bf16)(float)(lane + ks + pl + nb);
-                    } else {
-                        fb[nb][ks][pl] = img[((ks * 3 + pl) * 8 + 2 * wid + nb) * 64 + lane];
-                    }
+                    fb[nb][ks][pl] = img[((ks * 3 + pl) * 8 + 2 * wid + nb) * 64 + lane];
                 }
     } else {
         narrow_self_weights<KS>(p, lds, fb);
@@ -213,7 +200,7 @@ __device__ __forceinline__ void narrow_block(const NarrowParams &p, const bf16x8
         for (int r = wid; r < TR; r += 4) {
             const int64_t row = row0 + r;
             const f32x4 v = *reinterpret_cast<const f32x4 *>(so + r * 256 + 4 * lane);
-            if (row < p.N && (!(DC_NARROW_ABL & 4) || v[0] == 12345.678f)) *reinterpret_cast<f32x4 *>(p.out + row * p.ldo + 4 * lane) = v;
+            if (row < p.N) *reinterpret_cast<f32x4 *>(p.out + row * p.ldo + 4 * lane) = v;
         }
     };
     // Order inside an iteration (vector-memory operations retire in order, and hipcc's wait before the first use of the staged
@@ -223,7 +210,7 @@ __device__ __forceinline__ void narrow_block(const NarrowParams &p, const bf16x8
     int64_t prev_row0 = -1;
     for (; t < p.ntiles; t += gridDim.x) {
         const int64_t row0 = (int64_t)t * TR;
-        if (!(DC_NARROW_ABL & 8)) store_tile();         // (every wave is past the MFMAs of the previous tile: barrier B)
+        store_tile();                                   // (every wave is past the MFMAs of the previous tile: barrier B)
         if (prev_row0 >= 0) store_rows(prev_row0);
         if (!LATE && t + (int)gridDim.x < p.ntiles) load_tile(t + gridDim.x);
         lds_barrier();                               // A: the plane image is complete; the staging image has been read
@@ -250,10 +237,7 @@ __device__ __forceinline__ void narrow_block(const NarrowParams &p, const bf16x8
                 for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
                     for (int nb = 0; nb < 2; ++nb)
-                        if (!(DC_NARROW_ABL & 1))
-                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[mb][pa6[tt]], fb[nb][ks][pb6[tt]], acc[mb][nb], 0, 0, 0);
-                        else
-                            acc[mb][nb][tt] += (float)fa[mb][pa6[tt]][0] * (float)fb[nb][ks][pb6[tt]][0];
+                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[mb][pa6[tt]], fb[nb][ks][pb6[tt]], acc[mb][nb], 0, 0, 0);
         }
         if (LATE && t + (int)gridDim.x < p.ntiles) load_tile(t + gridDim.x);
         // epilogue: bias + ReLU, accumulators -> [TR][256] image (C/D layout: row (reg & 3) + 8 (reg >> 2) + 4 h, column c)
@@ -265,8 +249,7 @@ __device__ __forceinline__ void narrow_block(const NarrowParams &p, const bf16x8
                 for (int r = 0; r < 16; ++r) {
                     float v = acc[mb][nb][r] + bcol[nb];
                     if (relu) v = relu_keep_nan(v);
-                    if (!(DC_NARROW_ABL & 16) || r == 0)
-                        so[(mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 256 + 64 * wid + 32 * nb + c] = v;
+                    so[(mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 256 + 64 * wid + 32 * nb + c] = v;
                 }
         lds_barrier();                               // B: image complete; every wave has read its plane fragments
         prev_row0 = row0;
@@ -286,18 +269,11 @@ __global__ void __launch_bounds__(256, WPC) k_fwd_narrow_img(NarrowParams p, con
 // the image on its own: calls in which no pack launch happens (cached hop slab, a caller's own slab)
 __global__ void __launch_bounds__(256) k_narrow_wimage(NarrowImageParams q) { narrow_image_fill(q, (int)blockIdx.x); }
 
-// workgroups per CU of k_fwd_narrow_img: two where 256 registers hold the fragments (wpad 96 / 112); DC_NARROW_WPC=1
-// keeps the grid at one per CU (measurements)
-static int narrow_wpc() {
-    static const int v = env_int("DC_NARROW_WPC", 2) == 1 ? 1 : 2;
-    return v;
-}
-
 template <int KS, int WPC>
 static void narrow_img_launch(const NarrowParams &p0, const void *img, hipStream_t hs) {
     NarrowParams p = p0;
     p.ntiles = (int)((p.N + 31) / 32);
-    const int cap = 256 * (WPC == 2 ? narrow_wpc() : 1);
+    const int cap = 256 * WPC;              // workgroups per CU: two where 256 registers hold the fragments (wpad 96 / 112)
     const unsigned grid = (unsigned)(p.ntiles < cap ? p.ntiles : cap);
     DC_LAUNCH((k_fwd_narrow_img<KS, WPC>), dim3(grid), dim3(256), 0, hs, p, static_cast<const bf16x8 *>(img));
 }

@@ -22,16 +22,6 @@
 
 #pragma clang fp contract(off)
 
-// timing-only ablations (tools/exp/hop_chain_abl.py builds this file with -DDC_CHAIN_ABL=<bits>; results are wrong by
-// construction): 1 no block stores, 2 no neighbour slots at all, 4 no LDS write-back / barriers between hops,
-// 8 no source-block staging, 16 no id / weight loads, 32 LDS gathers but no arithmetic, 64 block stores to a
-// contiguous 128 KiB region per workgroup and hop (is the row-strided 128-byte store pattern what costs?), 128 ids /
-// weights made up in registers instead of loaded (do the in-loop VMEM loads couple the compute to the stores?),
-// 256 row maxima formed but not published (what do the atomics cost?  ~2 us per launch, profiles/r05/o_chain_rowmax_atomics.txt)
-#ifndef DC_CHAIN_ABL
-#define DC_CHAIN_ABL 0
-#endif
-
 namespace dc {
 
 constexpr int kChainCols = 32;        // columns per slice: 128-byte row pieces, one full cache line per store
@@ -77,10 +67,7 @@ __device__ __forceinline__ float4 lds_read4(unsigned addr) {
 __device__ __forceinline__ void store_piece(const float4 &a, __amdgpu_buffer_rsrc_t rs, unsigned off) {
     u32x4 av;
     av.x = __float_as_uint(a.x), av.y = __float_as_uint(a.y), av.z = __float_as_uint(a.z), av.w = __float_as_uint(a.w);
-    if (DC_CHAIN_ABL & 1)
-        asm volatile("" ::"v"(av.x), "v"(av.y), "v"(av.z), "v"(av.w));
-    else
-        __builtin_amdgcn_raw_buffer_store_b128(av, rs, off, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(av, rs, off, 0, 0);
 }
 
 // 8 lanes x 8 rows of per-lane maxima -> lane `sub` holds the maximum of the row of step `sub` (a transposing
@@ -101,9 +88,9 @@ __device__ __forceinline__ float rowmax_transpose(const float (&pm)[8], int sub)
     return fmaxf(keep, __shfl_xor(send, 4));
 }
 
+// (the row-maximum atomics cost ~2 us per launch, profiles/r05/o_chain_rowmax_atomics.txt)
 __device__ __forceinline__ void publish_rowmax(const float (&pm)[8], int sub, int steps, int row, int nn, float *rowmax) {
     const float rm = rowmax_transpose(pm, sub);
-    if (DC_CHAIN_ABL & 256) return;
     if (sub < steps && row < nn) atomicMax(reinterpret_cast<int *>(rowmax + row), __float_as_int(rm));
 }
 
@@ -128,17 +115,6 @@ struct Chunk {                        // ids and weights of 8 consecutive edges
 template <bool W>
 __device__ __forceinline__ void load_chunk(Chunk &c, __amdgpu_buffer_rsrc_t ro, __amdgpu_buffer_rsrc_t rw, int p) {
     // 4-byte aligned 16-byte loads, range-checked per dword against the arrays' size (past the end: 0)
-    if (DC_CHAIN_ABL & 16) {
-        c.i0 = c.i1 = c.w0 = c.w1 = u32x4{(unsigned)p, (unsigned)p, (unsigned)p, (unsigned)p} & 0u;
-        return;
-    }
-    if (DC_CHAIN_ABL & 128) {                                    // ids made up from the edge offset: no VMEM load, spread rows
-        const unsigned q = (unsigned)p / 6u;
-        c.i0 = u32x4{(q + 1) & 511u, (q + 14) & 511u, (q + 27) & 511u, (q + 40) & 511u};
-        c.i1 = u32x4{(q + 53) & 511u, (q + 66) & 511u, (q + 79) & 511u, (q + 92) & 511u};
-        c.w0 = c.w1 = u32x4{0x3e000000u, 0x3e000000u, 0x3e000000u, 0x3e000000u};
-        return;
-    }
     c.i0 = __builtin_amdgcn_raw_buffer_load_b128(ro, 4 * p, 0, 0);
     c.i1 = __builtin_amdgcn_raw_buffer_load_b128(ro, 4 * p + 16, 0, 0);
     if (W) {
@@ -167,7 +143,6 @@ __device__ __forceinline__ void chunk_slots(float4 &acc, const Chunk &c, int rem
     const unsigned wb[8] = {c.w0.x, c.w0.y, c.w0.z, c.w0.w, c.w1.x, c.w1.y, c.w1.z, c.w1.w};
     float4 v[NS];
     float ww[NS];
-    if (DC_CHAIN_ABL & 2) return;
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
         unsigned off = id[J0 + j] * (unsigned)RB + lbase;
@@ -178,11 +153,6 @@ __device__ __forceinline__ void chunk_slots(float4 &acc, const Chunk &c, int rem
         wt = valid ? wt : 0.0f;
         v[j] = lds_read4(off);
         ww[j] = wt;
-    }
-    if (DC_CHAIN_ABL & 32) {
-#pragma unroll
-        for (int j = 0; j < NS; ++j) asm volatile("" ::"v"(v[j].x), "v"(v[j].y), "v"(v[j].z), "v"(v[j].w), "v"(ww[j]));
-        return;
     }
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
@@ -247,7 +217,7 @@ k_hop_chain(ChainParams p) {
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
             const int row = rwave + RPW * s + grp;
-            if (row < nn && !(DC_CHAIN_ABL & 8))
+            if (row < nn)
                 __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + (int64_t)row * p.ld), DC_DMA_DST(smem + (rwave + RPW * s) * RB),
                                                  16, 0, 0);
         }
@@ -277,7 +247,7 @@ k_hop_chain(ChainParams p) {
     }
 
     const unsigned sbase = lds_addr(smem);
-    const unsigned lbase = sbase + 16u * sub - ((DC_CHAIN_ABL & 128) ? 0u : (unsigned)n0 * (unsigned)RB);   // LDS address of a neighbour's piece: id * RB + lbase
+    const unsigned lbase = sbase + 16u * sub - (unsigned)n0 * (unsigned)RB;   // LDS address of a neighbour's piece: id * RB + lbase
     const unsigned zsub = sbase + zoff + 16u * sub;
     const LdsWindow win{sbase + 16u * sub, (unsigned)nn * (unsigned)RB};
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -309,7 +279,6 @@ k_hop_chain(ChainParams p) {
             store_piece(a, rs, (unsigned)(rwave + RPW * s + grp) * ldb + dcol);             // streams out meanwhile
         }
         if (h + 1 == p.K) break;
-        if (DC_CHAIN_ABL & 4) continue;
         lds_barrier();                                           // every wave has read what it needs of block h
 #pragma unroll
         for (int s = 0; s < STEPS; ++s)
@@ -337,7 +306,6 @@ __device__ __forceinline__ void gcn_slots(float4 &acc, const uint4 &iv, float di
     const unsigned pk[4] = {iv.x, iv.y, iv.z, iv.w};
     float4 v[NS];
     float ww[NS];
-    if (DC_CHAIN_ABL & 2) return;
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
         const unsigned id = ((J0 + j) & 1) ? pk[(J0 + j) >> 1] >> 16 : pk[(J0 + j) >> 1] & 0xffffu;
@@ -369,13 +337,6 @@ k_hop_chain_gcn(ChainParams p) {
     float *blk = p.slab + (int64_t)n0 * p.ld + slice * kChainCols + 4 * sub;
     // LDS: slice [R][128 B] | zeros [128 B] | ids [R][8] u16 | dis [R + 1] f32 (16-byte padded) | {first edge, degree} [R]
     constexpr int kIds = (R + 1) * 128, kDis = kIds + R * 16, kBounds = kDis + ((R + 1) * 4 + 15) / 16 * 16;
-#ifdef DC_CHAIN_POISON
-    // diagnostic build (tools/r05): every byte of the workgroup's LDS starts as a quiet NaN, so that a read of LDS this
-    // launch has not written yet cannot pass for data
-    for (int i = threadIdx.x; i < (kBounds + R * 8) / 16; i += 1024)
-        reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0x7fc00000u, 0x7fc00000u, 0x7fc00000u, 0x7fc00000u);
-    __syncthreads();
-#endif
     // prologue without a table image, by wave role: waves 8-15 issue ALL the LDS-DMA of the slice (one instruction = 8 rows x 128 B, contiguous
     // in LDS), waves 0-7 build the tables.  hipcc makes a wave with LDS-DMA in flight wait for vmcnt(0) before each of
     // its own LDS accesses: with both jobs in every wave the tables' loads were only issued once the slice had landed.
@@ -399,7 +360,7 @@ k_hop_chain_gcn(ChainParams p) {
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
             const int r0 = rwave + 8 * s;
-            if (r0 + grp < nn && !(DC_CHAIN_ABL & 8))
+            if (r0 + grp < nn)
                 __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + (int64_t)(r0 + grp) * p.ld), DC_DMA_DST(smem + r0 * 128), 16, 0, 0);
         }
         if (threadIdx.x < 8)
@@ -424,27 +385,9 @@ k_hop_chain_gcn(ChainParams p) {
 #pragma unroll
         for (int s = 0; s < 2 * STEPS; ++s) {
             const int r0 = (wid - 8) * 16 * STEPS + 8 * s;      // the rows of waves 2 (wid - 8) and 2 (wid - 8) + 1
-#ifdef DC_CHAIN_REGSTAGE
-            // diagnostic build (tools/r06/chain_variants.sh): the same bytes through registers (global_load_dwordx4 +
-            // ds_write_b128) instead of LDS-DMA - does the rare difference need the DMA path?
             if (r0 + grp < nn)
-                *reinterpret_cast<float4 *>(smem + r0 * 128 + 16 * lane) =
-                    *reinterpret_cast<const float4 *>(src + (int64_t)(r0 + grp) * p.ld);
-#else
-            if (r0 + grp < nn && !(DC_CHAIN_ABL & 8))
                 __builtin_amdgcn_global_load_lds(DC_DMA_SRC(src + (int64_t)(r0 + grp) * p.ld), DC_DMA_DST(smem + r0 * 128), 16, 0, 0);
-#endif
         }
-#ifdef DC_CHAIN_DMA_READBACK
-        // diagnostic build: behind its own vmcnt(0) every DMA wave reads back the last piece it brought in, before the
-        // barrier releases the other waves' reads
-        DC_WAITVM(0);
-        {
-            const int r_last = (wid - 8) * 16 * STEPS + 8 * (2 * STEPS - 1);
-            const float4 v = *reinterpret_cast<const float4 *>(smem + r_last * 128 + 16 * lane);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w) : "memory");
-        }
-#endif
     } else {
         if (threadIdx.x < 8)
             *reinterpret_cast<float4 *>(smem + R * 128 + 16 * threadIdx.x) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -520,7 +463,6 @@ k_hop_chain_gcn(ChainParams p) {
             store_piece(a, rs, (unsigned)row * ldb + dcol);      // streams out while the next steps compute
         }
         if (h + 1 == p.K) break;
-        if (DC_CHAIN_ABL & 4) continue;
         lds_barrier();
 #pragma unroll
         for (int s = 0; s < STEPS; ++s)
@@ -535,13 +477,6 @@ k_hop_chain_gcn(ChainParams p) {
         const int sub2 = l2 & 7, grp2 = l2 >> 3;
         publish_rowmax(pm, sub2, STEPS, rwave + 8 * sub2 + grp2, nn, p.rowmax + n0);
     }
-#ifdef DC_CHAIN_POISON_END
-    // diagnostic build (tools/r05): leave quiet NaNs behind in the slice, so that a LATER workgroup on this CU that reads LDS
-    // it has not (yet) written cannot pass for data of the right magnitude; the prologue's timing stays what it is
-    lds_barrier();
-    for (int i = threadIdx.x; i < (R + 1) * 8; i += 1024)
-        reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0x7fc00000u, 0x7fc00000u, 0x7fc00000u, 0x7fc00000u);
-#endif
 }
 
 // the launch-log name of one instantiation, e.g. "k_hop_chain<true, 3, 8>", as a constant: the launch-site record
@@ -575,21 +510,16 @@ static bool launch_chain_gcn_steps(unsigned grid, hipStream_t stream, const Chai
     constexpr int R = 128 * STEPS;
     constexpr size_t lds = (size_t)(R + 1) * 128 + (size_t)R * 16 + ((size_t)(R + 1) * 4 + 15) / 16 * 16 + (size_t)R * 8;
     static_assert(lds <= 160 * 1024, "k_hop_chain_gcn: tables do not fit the LDS");
-#ifdef DC_CHAIN_LDS_TIGHT
-    constexpr size_t lds_req = lds;              // diagnostic build (tools/r05): only what the slice needs, as up to round 4
-#else
-    constexpr size_t lds_req = kChainLdsRequest;
-#endif
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hop_chain_gcn<STEPS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_req) != hipSuccess)
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainLdsRequest) != hipSuccess)
             return false;
         attr_set = true;
     }
     static constexpr ChainName name = chain_name("k_hop_chain_gcn<", -1, STEPS, 0);
     DC_LAUNCH_SITE(name.s);
-    hipLaunchKernelGGL((k_hop_chain_gcn<STEPS>), dim3(grid), dim3(1024), lds_req, stream, p);
+    hipLaunchKernelGGL((k_hop_chain_gcn<STEPS>), dim3(grid), dim3(1024), kChainLdsRequest, stream, p);
     return true;
 }
 

@@ -563,3 +563,15 @@ def test_dense_path_table(monkeypatch):
     for fi, k, fo, _ in _LAYER_SHAPES:
         wpad = ops.tag_slab_geometry(fi, k)[2]
         assert bool(L.dc_tag_linear_fwd_narrow_ok(fi, k + 1, wpad, fo)) == _narrow_ok(fi, k + 1, wpad, fo)
+
+
+def test_kernel_sources_carry_no_preprocessor_conditionals():
+    """Every file under ``csrc/`` is compiled one way only: what a reader sees is what the library runs."""
+    csrc = os.path.join(ROOT, "deformcontact_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*")))
+    assert len(files) >= 30
+    found = [f"{os.path.basename(f)}:{n}: {line.strip()}" for f in files
+             for n, line in enumerate(open(f, errors="replace"), 1)
+             if re.match(r"\s*#\s*(if|ifdef|ifndef|elif|else)\b", line)]
+    assert not found, ("preprocessor conditionals in the product sources (ablation, diagnostic and other variant builds "
+                       "belong in stand-alone kernels under tools/exp/):\n" + "\n".join(found))

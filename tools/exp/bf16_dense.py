@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time dc_tag_linear_fwd_bf16 on the configs[4] shape ([100k, 1024] x [256, 1024]^T) with padded / unpadded slab rows
-and bf16 / fp32 output.  DC_BF16_X=0/1 picks the 128 x 128 or the 256 x 256 kernel."""
+and bf16 / fp32 output.  The library picks the tile shape by tile count: 256 x 256 (k_fwd_bf16x) at this size."""
 import os
 import sys
 

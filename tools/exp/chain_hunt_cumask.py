@@ -78,7 +78,7 @@ def main():
             for s in range(STEPS):
                 if not torch.equal(cur[s], base[s]):
                     bad += 1
-                    # (round 6: with a -DDC_CHAIN_POISON build a NaN here = LDS read before its data had landed)
+                    # (round 6: with the LDS-poisoning diagnostic build of that round a NaN here = LDS read before its data had landed)
                     n_nan = int(torch.isnan(cur[s]).sum())
                     nans += n_nan > 0
                     d = (cur[s] - base[s]).abs()

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Time the wide forward-shaped fp16x2 block (dc_tag_linear_fwd_h2p -> k_fwd_h2d) and the wide dW block at the B = 32 shapes,
-on rotating slabs (operands from beyond the Infinity Cache), HIP events.  For A/B runs of variant libraries:
-    python tools/exp/run_with_lib.py <lib.so> tools/r06/dense_time.py"""
+on rotating slabs (operands from beyond the Infinity Cache), HIP events."""
 import os
 import sys
 
